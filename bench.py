@@ -1,5 +1,5 @@
-"""Benchmark: Shuffle(4) encode+decode of device-resident 256 MiB fp32 chunks,
-plus every other BASELINE.json configuration with its CPU baseline.
+"""Benchmark: Shuffle(4) encode+decode of device-resident 256 MiB fp32 chunks;
+with --full, also every other BASELINE.json configuration with its CPU baseline.
 
 Metric (BASELINE.json): "GiB/s encode+decode per GPU, device-resident fp32
 chunks (Shuffle, BitRound)", quoted on configs[1]: Shuffle(elementsize=4) on
@@ -13,7 +13,17 @@ aggregate_GiBps, frac_of_n_peak (HBM reads + writes / (physical GPUs x
 8 TB/s)), `ranks` (rank, local rank, host, pid, device, PCI location, UUID,
 elapsed) and `rehearsal` (true when ranks share a physical GPU).
 
-    python bench.py [--gpus N --steps K --warmup W] [--no-cpu] [--quick]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--quick]]
+
+A plain run sets up, warms up, times the K steps and prints the headline
+line (metric, value, ms_per_step = milliseconds per timed step, the rank
+record and the roofline of the timed launches).  --dump-outputs DIR then
+writes the encoded and the decoded buffer of the last timed step to
+DIR/encoded.npy and DIR/decoded.npy (float32, a fixed seeded sample of each;
+the inputs are seeded, so two builds can be compared output for output).
+--full adds everything else listed below to the same line; --no-cpu and
+--quick trim a --full run.
 
 --gpus N > 1 without a launcher: bench.py starts N rank processes itself
 (before anything touches the GPU), one per GPU (LOCAL_RANK = rank), with the
@@ -27,6 +37,7 @@ Printed (rank 0): ONE JSON line with the contract's keys plus
                 duration (a HIP event pair on the launch stream bracketing
                 the timed region); peak 8 TB/s; `traffic` = HBM bytes per
                 launch from the rocprofv3 PMC summary under profiles/;
+and, with --full, the in-run copy calibration in `roofline` and
   cpu_baseline  the build's own scalar C restatement (oracle/ncoracle.c,
                 kind "port") of _shuffle.pyx:11-30 on 1 host core and on P
                 processes, bounded sample of the same workload;
@@ -373,6 +384,36 @@ def trace_roofline():
             "trace_file": os.path.relpath(files[-1], ROOT), "trace_kernels": per}
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept per dumped array (16 MiB as float32)
+DUMP_EDGE = 1 << 16  # of them, the first and the last elements of the array
+
+
+def dump_index(n: int) -> "torch.Tensor | None":
+    """Positions dump_outputs keeps of an n-element array (None: all of it)."""
+    if n <= DUMP_SAMPLE:
+        return None
+    g = torch.Generator().manual_seed(0)
+    mid = torch.randint(DUMP_EDGE, n - DUMP_EDGE, (DUMP_SAMPLE - 2 * DUMP_EDGE,), generator=g)
+    return torch.cat([torch.arange(DUMP_EDGE), mid.sort().values, torch.arange(n - DUMP_EDGE, n)])
+
+
+def dump_outputs(path: str, rank: int, arrays: dict) -> None:
+    """--dump-outputs: write what the last timed step left in its output
+    buffers as <path>/<name>.npy (rank 0; <name>_rank<r>.npy for the others),
+    float32.  An array longer than DUMP_SAMPLE elements is sampled: its first
+    and last DUMP_EDGE elements plus positions drawn once from a fixed seed,
+    the same positions in every run, in ascending order.  Encoded bytes are
+    stored as their values 0..255 (exact in float32)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        idx = dump_index(flat.numel())
+        if idx is not None:
+            flat = flat[idx.to(flat.device)]
+        suffix = "" if rank == 0 else f"_rank{rank}"
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), flat.to(torch.float32).cpu().numpy())
+
+
 def run_step_timing(args, dev, dist, rank):
     from numcodecs_amd import Shuffle
 
@@ -414,6 +455,9 @@ def run_step_timing(args, dev, dist, rank):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     gpu_ms = ev0.elapsed_time(ev1)
+    if args.dump_outputs:
+        last = (args.steps - 1) % sets  # the buffer set the last timed step wrote
+        dump_outputs(args.dump_outputs, rank, {"encoded": encs[last], "decoded": decs[last].view(torch.float32)})
     del ins, encs, decs
     return elapsed, gpu_ms / (2 * args.steps), gpu_ms * 1e-3
 
@@ -802,24 +846,32 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: the CPU baselines, c5_sharded, the "
+                         "copy calibration of the roofline and (N = 1) the cfg_* blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the output buffers of the last timed step to DIR/<name>.npy (float32, sampled)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline legs")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="timed CPU work per leg and config")
     ap.add_argument("--cpu-procs", type=int, default=min(16, os.cpu_count() or 1),
                     help="processes of the parallel CPU leg (the GPU box's CPU share is 16)")
-    ap.add_argument("--quick", action="store_true", help="headline and c5_sharded only (no cfg_* block)")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline and c5_sharded only (no cfg_* block)")
     ap.add_argument("--c5-chunks", type=int, default=8192)
     ap.add_argument("--c5-steps", type=int, default=5)
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the rank launch and the C5 partition (no GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    want_cpu = args.full and not args.no_cpu
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
-        # the launcher parent never touches the GPU: it times the CPU legs
-        # (bounded: the headline's C2 f32 and C5) before it starts the ranks
-        # and hands them to rank 0 through a file
+        # the launcher parent never touches the GPU: with --full it times the
+        # CPU legs (bounded: the headline's C2 f32 and C5) before it starts
+        # the ranks and hands them to rank 0 through a file
         extra = {}
-        if not args.no_cpu:
+        if want_cpu:
             import tempfile
 
             cpu = cpu_baselines(args.cpu_procs, args.cpu_seconds, only=CPU_CONFIGS_MULTI)
@@ -837,12 +889,12 @@ def main():
     if world_env != args.gpus:
         raise SystemExit(f"bench.py --gpus {args.gpus} but WORLD_SIZE={world_env}")
 
-    # the CPU legs fork, so they run before anything touches the GPU: at N = 1
-    # all of them; at N > 1 the launcher parent's (self-launch) or, under
-    # torch.distributed.run, rank 0's own before it joins the process group
+    # the CPU legs (--full) fork, so they run before anything touches the GPU:
+    # at N = 1 all of them; at N > 1 the launcher parent's (self-launch) or,
+    # under torch.distributed.run, rank 0's own before it joins the process group
     cpu = load_cpu(os.environ.get("MCODEC_BENCH_CPU_JSON"))
     rank_env = int(os.environ.get("RANK", "0"))
-    if cpu is None and rank_env == 0 and not args.no_cpu:
+    if cpu is None and rank_env == 0 and want_cpu:
         if world_env == 1 and not args.dry_run:
             cpu = cpu_baselines(args.cpu_procs, args.cpu_seconds)
         elif world_env > 1:
@@ -867,22 +919,20 @@ def main():
     head_ranks = gather_ranks(dist, dict(ident, elapsed_s=round(elapsed, 6), gpu_event_s=round(gpu_s, 6)))
     head_scale = scaling_fields(head_ranks, args.steps * 4 * CHUNK, args.steps * 2 * CHUNK, t, on_gpu=True)
 
-    c5_el, c5_launch_ms, c5_local, c5_gpu_s = run_c5_sharded(args.c5_steps, 1, args.c5_chunks, dev, dist, rank,
-                                                              world)
-    c5_t = max_over_ranks(dist, c5_el)
-    c5_launch_ms = max_over_ranks(dist, c5_launch_ms)
-    c5_ranks = gather_ranks(dist, {"rank": rank, "host": ident["host"], "pci": ident["pci"],
-                                   "chunks": c5_local, "elapsed_s": round(c5_el, 6),
-                                   "gpu_event_s": round(c5_gpu_s, 6)})
-    c5_ev_max = max(r["gpu_event_s"] for r in c5_ranks)
+    if args.full:
+        # everything behind --full that every rank takes part in: the sharded C5
+        c5_el, c5_launch_ms, c5_local, c5_gpu_s = run_c5_sharded(args.c5_steps, 1, args.c5_chunks, dev, dist,
+                                                                  rank, world)
+        c5_t = max_over_ranks(dist, c5_el)
+        c5_launch_ms = max_over_ranks(dist, c5_launch_ms)
+        c5_ranks = gather_ranks(dist, {"rank": rank, "host": ident["host"], "pci": ident["pci"],
+                                       "chunks": c5_local, "elapsed_s": round(c5_el, 6),
+                                       "gpu_event_s": round(c5_gpu_s, 6)})
+        c5_ev_max = max(r["gpu_event_s"] for r in c5_ranks)
 
     if rank == 0:
         achieved = 2 * CHUNK / (launch_ms * 1e-3) / 1e9  # GB/s per launch
         traffic, traffic_src = pmc_traffic()
-        ceiling = copy_ceiling(dev)
-        c5_bytes = args.c5_steps * 2 * args.c5_chunks * MiB
-        c5_alg = c5_local * (2 * MiB + 4)  # rank 0's chunks per launch: payload in + out (+ footer)
-        c5_phys = head_scale["physical_gpus"]
         result = {
             "metric": METRIC,
             "value": round(value, 2),
@@ -895,7 +945,7 @@ def main():
             "event_aggregate_GiBps": head_scale["event_aggregate_GiBps"],
             "host_minus_event_s": head_scale["host_minus_event_s"],
             "frac_of_n_peak": head_scale["frac_of_n_peak"],
-            "physical_gpus": c5_phys,
+            "physical_gpus": head_scale["physical_gpus"],
             "rehearsal": head_scale["rehearsal"],
             "ranks": head_ranks,
             "steps": args.steps,
@@ -922,12 +972,18 @@ def main():
                 "traffic": traffic,
                 "traffic_source": traffic_src,
                 "mean_launch_ms": round(launch_ms, 4),
-                "copy_ceiling_GBps": ceiling["ceiling_GBps"],
-                "frac_of_copy_ceiling": round(achieved / ceiling["ceiling_GBps"], 4),
-                "copy_calibration": ceiling,
                 **(trace_roofline() or {"trace_frac": None}),
             },
-            "c5_sharded": {
+        }
+        if args.full:
+            ceiling = copy_ceiling(dev)
+            result["roofline"].update(copy_ceiling_GBps=ceiling["ceiling_GBps"],
+                                      frac_of_copy_ceiling=round(achieved / ceiling["ceiling_GBps"], 4),
+                                      copy_calibration=ceiling)
+            c5_bytes = args.c5_steps * 2 * args.c5_chunks * MiB
+            c5_alg = c5_local * (2 * MiB + 4)  # rank 0's chunks per launch: payload in + out (+ footer)
+            c5_phys = head_scale["physical_gpus"]
+            result["c5_sharded"] = {
                 "GiBps": round(c5_bytes / GiB / c5_t, 1),
                 "per_gpu_GiBps": round(c5_bytes / GiB / c5_t / c5_phys, 1),
                 "event_GiBps": round(c5_bytes / GiB / c5_ev_max, 1),
@@ -944,10 +1000,9 @@ def main():
                              "Shuffle(4)+Fletcher32 encode + fused verify+unshuffle decode with the per-chunk "
                              "verdict compared on the device and read back (raising on a mismatch) every step"),
                 "ranks": c5_ranks,
-            },
-        }
-        result["cpu_baseline"] = headline_cpu(cpu)
-        if world > 1:
+            }
+            result["cpu_baseline"] = headline_cpu(cpu)
+        if args.full and world > 1:
             # the N > 1 line keeps a bounded per-config block: the headline's
             # C2 f32 (rank 0's launches) and the sharded C5, each beside its
             # CPU baseline timed on this node before the ranks started
@@ -959,7 +1014,7 @@ def main():
             result["cfg_C5"] = _cfg(2 * c5_local * MiB / GiB / (2 * c5_call), c5_call, c5_call,
                                     2 * c5_alg, "k_shuffle_f32_enc / k_f32_unshuffle (rank 0's chunk range)",
                                     cpu, "C5", f"rank 0's {c5_local} of {args.c5_chunks} chunks per call")
-        if world == 1 and not args.quick:
+        if args.full and world == 1 and not args.quick:
             result.update(config_workloads(dev, cpu))
             result["cfg_e2e"] = end_to_end(dev, cpu)
             result["cfg_next"] = next_rows(dev)
