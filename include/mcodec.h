@@ -537,6 +537,43 @@ enum mc_blosc_mode { MC_BLOSC_NOSHUFFLE = 0, MC_BLOSC_SHUFFLE = 1, MC_BLOSC_BITS
 int mc_blosc_filter(const void *src, void *dst, size_t nbytes, size_t typesize,
                     size_t blocksize, int mode, int forward, mc_stream_t stream);
 
+/* ---- Blosc decompression: LZ4 / stored frames (blosc.pyx:274-326) -------- */
+/* Decode a batch of Blosc1 frames whose compressor format is 1 (lz4 / lz4hc)
+ * or that are memcpyed, into their still-filtered block bytes: one plan
+ * launch (one thread per Blosc block: the stream descriptors, validated
+ * against each frame's length) and one decode launch (one wave per stream)
+ * for the whole batch.  mc_blosc_filter(forward = 0) then inverts the shuffle.
+ *   frames       device: the frames' bytes, concatenated
+ *   frame_table  device, 8-B aligned: nframes records of 48 bytes, one per
+ *                frame, from the 16-byte header the caller read on the host:
+ *                u64 src_off, src_len (the frame inside `frames`), u64 dst
+ *                (device address of the frame's nbytes output bytes), u32
+ *                nbytes, blocksize, typesize, flags, u32 block_base,
+ *                stream_base (running sums of the frames' block and stream
+ *                counts: nblocks = ceil(nbytes / blocksize); a full block has
+ *                typesize streams when flags & 0x10 is clear, typesize <= 16
+ *                and blocksize / typesize >= 128, every other block one;
+ *                a memcpyed frame one per block).  Frames with nbytes == 0
+ *                are left out.
+ *   nblocks, nstreams  the batch's totals; max_stream the largest stream's
+ *                uncompressed size (sizes the LDS history ring)
+ *   workspace    device, 8-B aligned, mc_blosc_decode_workspace(nstreams) bytes
+ *   err          device: 2 * nframes int32, zeroed here; frame i's first
+ *                violation leaves err[2i] = a positive code (csrc/mc_lz4.h)
+ *                and err[2i+1] = the stream's index in the batch.  A rejected
+ *                stream writes nothing beyond its own output range, and
+ *                nothing outside a frame is read.
+ * Returns a launch status; the error record is valid once the stream has
+ * run.  Block sizes of 2^30 and above are refused (MC_EINVAL).
+ * Present from this release on; mc_abi_version() is unchanged, callers find
+ * the pair by symbol. */
+size_t mc_blosc_decode_workspace(size_t nstreams);
+int mc_blosc_decode_batch(const void *frames, const void *frame_table,
+                          size_t nframes, size_t nblocks, size_t nstreams,
+                          size_t max_stream, void *workspace,
+                          size_t workspace_bytes, int32_t *err,
+                          mc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

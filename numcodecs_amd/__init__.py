@@ -57,6 +57,7 @@ from .packbits import PackBits
 register_codec(PackBits)
 
 from . import batch  # noqa: E402,F401
+from . import blosc  # noqa: E402,F401  (Blosc decode: LZ4 / stored frames; blosc.register() registers it)
 from . import blosc_shuffle  # noqa: E402,F401  (Blosc's per-block shuffle filters)
 from . import chunks  # noqa: E402,F401  (Zarr-style batched / host-streamed chunk pipelines)
 from . import graphs  # noqa: E402,F401  (HIP-graph captured chunk pipelines)
@@ -79,6 +80,7 @@ __all__ = [
     "Shuffle",
     "UnknownCodecError",
     "batch",
+    "blosc",
     "blosc_shuffle",
     "chunks",
     "graphs",

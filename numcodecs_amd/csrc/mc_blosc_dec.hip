@@ -1,0 +1,218 @@
+// mc_blosc_dec.hip -- Blosc1 frames (LZ4 / stored) -> still-filtered block
+// bytes on the device, for a whole batch of frames: one plan launch plus one
+// decode launch.  The frame and LZ4 rules, the sequence parser, the validity
+// predicate and the plan walker live in mc_lz4.h (compiled for the host too,
+// tests/native_lz4).  The inverse shuffle is mc_blosc_filter's job.
+//
+// plan:   one thread per Blosc block of the batch; writes one mc_lz4_stream
+//         descriptor per stream, everything validated against the frame length.
+// decode: one wave (a 64-lane workgroup) per stream, wave-uniform control
+//         flow.  The sequence header is parsed once per wave out of a 64-byte
+//         source window (one coalesced load, the next window loaded ahead,
+//         bytes picked with v_readlane); the lanes then copy literals and
+//         matches 64 bytes a step.  The stream's history lives in an LDS ring of min(pow2 >= stream, 64 KiB)
+//         bytes: matches are served from the ring (LZ4 offsets are <= 65535),
+//         never from global memory, and every produced byte is also streamed
+//         to global memory.  Each step's LDS reads are complete before its LDS
+//         writes issue (the written value is the read one), and lds_order()
+//         -- s_waitcnt lgkmcnt(0) behind a compiler memory barrier; the LDS
+//         runs one wave's instructions in issue order -- orders the writes
+//         before the next step's reads.
+//         A match with offset < 64 is copied in the replicating form (lane i
+//         reads start + i % offset): it only reads bytes that existed before
+//         the match began.
+#include "mc_common.h"
+#include "mc_lz4.h"
+
+namespace {
+
+constexpr uint32_t WAVE = 64;
+constexpr uint32_t RING_MAX = 65536;
+
+MC_DEV uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+MC_DEV void record_error(int32_t *err, uint32_t frame, int code, uint32_t stream) {
+  // first error of a frame wins; plain vector atomics / stores
+  if (atomicCAS(reinterpret_cast<int *>(&err[2 * frame]), 0, code) == 0) err[2 * frame + 1] = (int32_t)stream;
+}
+
+__global__ void __launch_bounds__(MC_BLOCK)
+plan_kernel(const uint8_t *__restrict__ frames, const mc_blosc_frame *__restrict__ table, uint32_t nframes,
+            uint32_t nblocks_total, mc_lz4_stream *__restrict__ streams, uint32_t nstreams_total,
+            int32_t *__restrict__ err) {
+  const uint32_t b = blockIdx.x * MC_BLOCK + threadIdx.x;
+  if (b >= nblocks_total) return;
+  // the frame whose [block_base, next block_base) holds b
+  uint32_t lo = 0, hi = nframes - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (table[mid].block_base <= b) lo = mid; else hi = mid - 1;
+  }
+  const mc_blosc_frame f = table[lo];
+  uint32_t bad = 0;
+  const int e = mc_blosc_plan_block(frames, f, lo, b - f.block_base, streams, nstreams_total, &bad);
+  if (e != MC_LZ4_OK) record_error(err, lo, e, bad);
+}
+
+// Orders this wave's LDS writes before its later LDS reads: the LDS executes
+// one wave's instructions in issue order, the wait makes them complete, and
+// the "memory" clobber keeps the compiler from moving an access across.
+// (A workgroup barrier orders them too; its fence also waits for the streamed
+// global stores, which nothing here needs.  Measured the same on MI355X.)
+MC_DEV void lds_order() { __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// the source stream through a 64-byte window held one byte per lane; the 64
+// bytes after it are loaded ahead, so that a refill seldom waits for memory
+struct wave_reader {
+  const uint8_t *src;
+  uint32_t n, base, lane;
+  uint32_t w, ahead;
+  MC_DEV uint32_t load(uint32_t at) { return (at + lane < n) ? src[at + lane] : 0u; }  // at <= n < 2^31
+  MC_DEV void start() {
+    base = 0;
+    w = load(0);
+    ahead = load(WAVE < n ? WAVE : n);
+  }
+  MC_DEV uint32_t byte(uint32_t i) {
+    if (i - base >= WAVE) {  // wave-uniform: i and base are
+      if (i - base < 2 * WAVE) {
+        base += WAVE;
+        w = ahead;
+      } else {
+        base = i;
+        w = load(i);
+      }
+      ahead = load(n - base > WAVE ? base + WAVE : n);
+    }
+    return (uint32_t)__builtin_amdgcn_readlane((int)w, (int)uni(i - base));
+  }
+};
+
+__global__ void __launch_bounds__(WAVE)
+decode_kernel(const uint8_t *__restrict__ frames, const mc_lz4_stream *__restrict__ streams, uint32_t nstreams,
+              uint32_t ring_mask, int32_t *__restrict__ err) {
+  extern __shared__ uint8_t ring[];
+  const uint32_t sidx = blockIdx.x, lane = threadIdx.x;
+  if (sidx >= nstreams) return;
+  const mc_lz4_stream d = streams[sidx];
+  if (!(d.flags & MC_LZ4_S_VALID)) return;
+  const uint8_t *src = frames + d.src_off;
+  uint8_t *dst = reinterpret_cast<uint8_t *>((uintptr_t)d.dst);
+  const uint32_t n = uni(d.cbytes), usize = uni(d.usize);
+  if (d.flags & MC_LZ4_S_RAW) {  // cbytes == usize (plan)
+    for (uint32_t k = lane; k < usize; k += WAVE) dst[k] = src[k];
+    return;
+  }
+  wave_reader rd{src, n, 0u, lane, 0u, 0u};
+  rd.start();
+  uint32_t ip = 0, op = 0;
+  int e = MC_LZ4_OK;
+  while (ip < n) {
+    mc_lz4_seq s;
+    e = mc_lz4_parse(rd, n, ip, &s);
+    if (e == MC_LZ4_OK) e = mc_lz4_check(s, op, usize);
+    e = (int)uni((uint32_t)e);
+    if (e != MC_LZ4_OK) break;  // nothing of the sequence is copied
+    const uint32_t lit_pos = uni(s.lit_pos), lit_len = uni(s.lit_len);
+    const uint32_t offset = uni(s.offset), match_len = uni(s.match_len);
+    // literals: source -> ring + global; a short run that the window still
+    // holds comes out of its registers (no memory latency on the chain)
+    if (lit_len && lit_pos >= rd.base && lit_pos - rd.base + lit_len <= WAVE) {
+      const uint8_t v = (uint8_t)__shfl(rd.w, (int)((lit_pos - rd.base + lane) & (WAVE - 1)), WAVE);
+      if (lane < lit_len) {
+        ring[(op + lane) & ring_mask] = v;
+        dst[op + lane] = v;
+      }
+    } else {
+      for (uint32_t k = 0; k < lit_len; k += WAVE) {
+        const uint32_t i = k + lane;
+        if (i < lit_len) {
+          const uint8_t v = src[lit_pos + i];
+          ring[(op + i) & ring_mask] = v;
+          dst[op + i] = v;
+        }
+      }
+    }
+    op += lit_len;
+    if (lit_len) lds_order();
+    // match: ring -> ring + global
+    if (offset >= WAVE) {
+      // 64 bytes a step: a step reads only bytes of earlier steps (offset >= 64)
+      for (uint32_t k = 0; k < match_len; k += WAVE) {
+        const uint32_t i = k + lane;
+        if (i < match_len) {
+          const uint8_t v = ring[(op + i - offset) & ring_mask];
+          ring[(op + i) & ring_mask] = v;
+          dst[op + i] = v;
+        }
+        lds_order();
+      }
+    } else if (match_len) {
+      // replicating form: only the `offset` bytes before the match are read
+      // (lane p < offset keeps byte p of them; a long match may wrap the ring
+      // over them, so they are read once, before anything is written)
+      uint32_t ph = lane % offset;  // (k + lane) % offset
+      const uint32_t step = WAVE % offset;
+      const uint32_t pat = ring[(op - offset + ph) & ring_mask];
+      for (uint32_t k = 0; k < match_len; k += WAVE) {
+        const uint32_t i = k + lane;
+        const uint8_t v = (uint8_t)__shfl(pat, (int)ph, WAVE);
+        if (i < match_len) {
+          ring[(op + i) & ring_mask] = v;
+          dst[op + i] = v;
+        }
+        ph += step;
+        if (ph >= offset) ph -= offset;
+      }
+      lds_order();
+    }
+    op += match_len;
+    ip = uni(s.next);
+  }
+  if (e == MC_LZ4_OK && op != usize) e = MC_LZ4_E_SIZE;
+  if (e != MC_LZ4_OK && lane == 0) record_error(err, d.frame, e, sidx);
+}
+
+uint32_t ring_bytes(size_t max_stream) {
+  uint32_t r = 256;
+  while (r < max_stream && r < RING_MAX) r <<= 1;
+  return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mc_blosc_decode_workspace(size_t nstreams) { return nstreams * sizeof(mc_lz4_stream) + 16; }
+
+int mc_blosc_decode_batch(const void *frames, const void *frame_table, size_t nframes, size_t nblocks,
+                          size_t nstreams, size_t max_stream, void *workspace, size_t workspace_bytes,
+                          int32_t *err, mc_stream_t stream) {
+  if (nframes == 0 || nblocks == 0) return MC_OK;
+  if (!frames || !frame_table || !workspace || !err) return MC_EINVAL;
+  if (nframes > 0x7fffffffu || nblocks > 0x7fffffffu || nstreams > 0x7fffffffu || nstreams < nblocks)
+    return MC_EINVAL;
+  if (max_stream == 0 || max_stream >= MC_LZ4_MAX_USIZE) return MC_EINVAL;
+  if (((uintptr_t)workspace & 7) || ((uintptr_t)frame_table & 7)) return MC_EINVAL;
+  if (workspace_bytes < mc_blosc_decode_workspace(nstreams)) return MC_ENOSPC;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = mc_hip_status(hipMemsetAsync(err, 0, nframes * 2 * sizeof(int32_t), st));
+  if (rc != MC_OK) return rc;
+  // a descriptor the plan does not write stays invalid (flags 0) and is skipped
+  rc = mc_hip_status(hipMemsetAsync(workspace, 0, nstreams * sizeof(mc_lz4_stream), st));
+  if (rc != MC_OK) return rc;
+  const uint8_t *fr = static_cast<const uint8_t *>(frames);
+  const mc_blosc_frame *table = static_cast<const mc_blosc_frame *>(frame_table);
+  mc_lz4_stream *streams = static_cast<mc_lz4_stream *>(workspace);
+  const unsigned pgrid = (unsigned)((nblocks + MC_BLOCK - 1) / MC_BLOCK);
+  hipLaunchKernelGGL(plan_kernel, dim3(pgrid), dim3(MC_BLOCK), 0, st, fr, table, (uint32_t)nframes,
+                     (uint32_t)nblocks, streams, (uint32_t)nstreams, err);
+  rc = mc_last_launch();
+  if (rc != MC_OK) return rc;
+  const uint32_t rb = ring_bytes(max_stream);
+  hipLaunchKernelGGL(decode_kernel, dim3((unsigned)nstreams), dim3(WAVE), rb, st, fr, streams,
+                     (uint32_t)nstreams, rb - 1, err);
+  return mc_last_launch();
+}
+
+}  // extern "C"
