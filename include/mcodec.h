@@ -35,6 +35,8 @@
  *   mc_packbits / mc_unpackbits .... packbits.py:33-82 PackBits.encode/decode
  *   mc_blosc_filter ................ blosc.pyx:67-71,211-326 SHUFFLE / BITSHUFFLE as
  *                                    c-blosc applies them per block (shuffle.c)
+ *   mc_blosc_decode_batch .......... blosc.pyx:274-326 decompress (lz4 / lz4hc / stored)
+ *   mc_blosc_encode_batch .......... blosc.pyx:211-272 compress (lz4)
  *   *_batch ........................ no reference counterpart: the Zarr caller loops
  *                                    Codec.encode per chunk; these run B equal-size
  *                                    chunks in one launch (chunk b at base + b*stride).
@@ -573,6 +575,44 @@ int mc_blosc_decode_batch(const void *frames, const void *frame_table,
                           size_t max_stream, void *workspace,
                           size_t workspace_bytes, int32_t *err,
                           mc_stream_t stream);
+
+/* ---- Blosc compression: LZ4 frames (blosc.pyx:211-272) ------------------- */
+/* Encode a batch of already-filtered buffers (mc_blosc_filter(forward = 1))
+ * as Blosc1 LZ4 frames: one compress launch (one wave per stream, LZ4 blocks
+ * into scratch), one layout launch (one workgroup per frame: stream offsets,
+ * bstarts, header, the memcpyed decision) and one gather launch (one
+ * workgroup per stream) for the whole batch.  A stream that does not get
+ * smaller is stored raw; a frame whose compressed form would exceed
+ * nbytes + 16 bytes is stored memcpyed (header + the unfiltered bytes).
+ *   src          base the records' src / raw fields are added to (NULL: they
+ *                are absolute device addresses)
+ *   frame_table  device, 8-B aligned: nframes records of 56 bytes, one per
+ *                frame with nbytes > 0: u64 src (the filtered bytes), u64 raw
+ *                (the unfiltered bytes), u64 dst (device address of the
+ *                frame's output slot of nbytes + 16 bytes; nothing is written
+ *                past it), u64 scratch_off (the frame's nbytes scratch bytes,
+ *                an offset into the workspace's scratch area), u32 nbytes,
+ *                blocksize, typesize, flags (the header's; bit 1 forces a
+ *                memcpyed frame), u32 block_base, stream_base (running sums
+ *                of the frames' block / stream counts, counted as for
+ *                mc_blosc_decode_batch).  The frames' slots, scratch ranges
+ *                and index ranges must not overlap.
+ *   nblocks, nstreams  the batch's totals
+ *   workspace    device, 8-B aligned, mc_blosc_encode_workspace(nstreams,
+ *                scratch_bytes) bytes: the scratch area is its last
+ *                scratch_bytes bytes
+ *   cbytes_out   device: nframes u32, frame i's length once the stream has
+ *                run; 0 when its record was refused (blocksize 0 or >= 2^30,
+ *                typesize outside 1..255, a split blocksize that is no
+ *                multiple of typesize, index or scratch ranges outside the
+ *                batch's): nothing of such a frame is written.
+ * Returns a launch status.  Present from this release on; mc_abi_version()
+ * is unchanged, callers find the pair by symbol. */
+size_t mc_blosc_encode_workspace(size_t nstreams, size_t scratch_bytes);
+int mc_blosc_encode_batch(const void *src, const void *frame_table,
+                          size_t nframes, size_t nblocks, size_t nstreams,
+                          void *workspace, size_t workspace_bytes,
+                          uint32_t *cbytes_out, mc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -181,6 +181,8 @@ _SIGNATURES = {
     "mc_unpackbits": [_c_vp, _c_size, _c_vp, _c_size, _c_vp],
     "mc_blosc_decode_workspace": [_c_size],
     "mc_blosc_decode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp],
+    "mc_blosc_encode_workspace": [_c_size, _c_size],
+    "mc_blosc_encode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp],
 }
 _RESTYPES = {
     "mc_host_device_pointer": ctypes.c_void_p,
@@ -196,6 +198,7 @@ _RESTYPES = {
     "mc_fso_delta_shuffle_decode_batch_workspace": ctypes.c_size_t,
     "mc_checksum32_workspace": ctypes.c_size_t,
     "mc_blosc_decode_workspace": ctypes.c_size_t,
+    "mc_blosc_encode_workspace": ctypes.c_size_t,
 }
 
 EXPORTED = tuple(_SIGNATURES)
