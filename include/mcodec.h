@@ -37,6 +37,8 @@
  *                                    c-blosc applies them per block (shuffle.c)
  *   mc_blosc_decode_batch .......... blosc.pyx:274-326 decompress (lz4 / lz4hc / stored)
  *   mc_blosc_encode_batch .......... blosc.pyx:211-272 compress (lz4)
+ *   mc_lz4_encode_batch ............ lz4.pyx:44-114 compress
+ *   mc_lz4_decode_batch ............ lz4.pyx:117-193 decompress
  *   *_batch ........................ no reference counterpart: the Zarr caller loops
  *                                    Codec.encode per chunk; these run B equal-size
  *                                    chunks in one launch (chunk b at base + b*stride).
@@ -613,6 +615,62 @@ int mc_blosc_encode_batch(const void *src, const void *frame_table,
                           size_t nframes, size_t nblocks, size_t nstreams,
                           void *workspace, size_t workspace_bytes,
                           uint32_t *cbytes_out, mc_stream_t stream);
+
+/* ---- LZ4 codec: a size word + one LZ4 block per chunk (lz4.pyx) ---------- */
+/* Encode a batch of chunks as `lz4` frames (u32 LE nbytes, then one LZ4
+ * block): one compress launch (one wave per 64 KiB segment of the batch, LZ4
+ * sequences into scratch), one layout launch (one workgroup per chunk: the
+ * literal carry across segments, the pieces' offsets, the exact frame length,
+ * the size word) and one gather launch (one workgroup per segment) for the
+ * whole batch.  The rules are csrc/mc_lz4_codec.h's.
+ *   src          base the records' src field is added to (NULL: absolute
+ *                device addresses)
+ *   chunk_table  device, 8-B aligned: nchunks records of 40 bytes, one per
+ *                chunk with nbytes > 0: u64 src, u64 dst (device address of
+ *                the frame's slot), u64 scratch_off (the chunk's nbytes
+ *                scratch bytes, an offset into the workspace's scratch area),
+ *                u32 nbytes (< 2^30), u32 dst_cap (the slot's size; 4 +
+ *                nbytes + nbytes / 255 + 16 always suffices; nothing is
+ *                written past it), u32 seg_base (running sum of the chunks'
+ *                segment counts, ceil(nbytes / 65536)), u32 reserved.  The
+ *                chunks' slots, scratch ranges and index ranges must not
+ *                overlap.
+ *   nsegments    the batch's total
+ *   workspace    device, 8-B aligned, mc_lz4_encode_workspace(nchunks,
+ *                nsegments, scratch_bytes) bytes: the scratch area is its
+ *                last scratch_bytes bytes
+ *   cbytes_out   device: nchunks u32, chunk i's frame length once the stream
+ *                has run; 0 when its record was refused (nbytes 0 or >= 2^30,
+ *                index or scratch ranges outside the batch's, a frame that
+ *                would not fit dst_cap): nothing of such a frame is written.
+ * Returns a launch status.  Present from this release on; mc_abi_version()
+ * is unchanged, callers find the pair by symbol. */
+size_t mc_lz4_encode_workspace(size_t nchunks, size_t nsegments, size_t scratch_bytes);
+int mc_lz4_encode_batch(const void *src, const void *chunk_table, size_t nchunks,
+                        size_t nsegments, void *workspace, size_t workspace_bytes,
+                        uint32_t *cbytes_out, mc_stream_t stream);
+
+/* Decode a batch of `lz4` frames: one plan launch (one thread per chunk: the
+ * size word re-read and checked against the record) and one decode launch
+ * (one wave per chunk; a single block is one serial chain).
+ *   frames       device: the frames' bytes, concatenated
+ *   chunk_table  device, 8-B aligned: nchunks records of 32 bytes: u64
+ *                src_off, src_len (the frame inside `frames`, size word
+ *                included), u64 dst (device address of the usize output
+ *                bytes), u32 usize (the size word, as the caller read it),
+ *                u32 reserved
+ *   max_usize    the largest usize of the batch (< 2^30; sizes the LDS ring)
+ *   workspace    device, 8-B aligned, mc_lz4_decode_workspace(nchunks) bytes
+ *   err          device: 2 * nchunks int32, zeroed here; chunk i leaves
+ *                err[2i] = 0 or a positive code (csrc/mc_lz4.h) and err[2i+1]
+ *                = the bytes its block produced.  A rejected sequence writes
+ *                nothing; nothing outside a frame is read and nothing outside
+ *                [dst, dst + usize) is written.
+ * Returns a launch status; the error record is valid once the stream has run. */
+size_t mc_lz4_decode_workspace(size_t nchunks);
+int mc_lz4_decode_batch(const void *frames, const void *chunk_table, size_t nchunks,
+                        size_t max_usize, void *workspace, size_t workspace_bytes,
+                        int32_t *err, mc_stream_t stream);
 
 #ifdef __cplusplus
 }

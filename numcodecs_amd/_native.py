@@ -183,6 +183,10 @@ _SIGNATURES = {
     "mc_blosc_decode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp],
     "mc_blosc_encode_workspace": [_c_size, _c_size],
     "mc_blosc_encode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp],
+    "mc_lz4_encode_workspace": [_c_size, _c_size, _c_size],
+    "mc_lz4_encode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp],
+    "mc_lz4_decode_workspace": [_c_size],
+    "mc_lz4_decode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp],
 }
 _RESTYPES = {
     "mc_host_device_pointer": ctypes.c_void_p,
@@ -199,6 +203,8 @@ _RESTYPES = {
     "mc_checksum32_workspace": ctypes.c_size_t,
     "mc_blosc_decode_workspace": ctypes.c_size_t,
     "mc_blosc_encode_workspace": ctypes.c_size_t,
+    "mc_lz4_encode_workspace": ctypes.c_size_t,
+    "mc_lz4_decode_workspace": ctypes.c_size_t,
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -12,7 +12,8 @@ launch per shuffled frame) and compressed, laid out and gathered by
 csrc/mc_blosc_enc.hip (three launches for a whole batch).  The frames are
 valid Blosc1 LZ4 frames that any Blosc reader decodes; they are not byte-equal
 to c-blosc's (the match finder differs).  The other Blosc compressors
-(blosclz, lz4hc, snappy, zlib, zstd) are not built: DESIGN.md §7.
+(blosclz, lz4hc, snappy, zlib, zstd) are not built: DESIGN.md §7.  The
+stand-alone ``lz4`` codec is :mod:`numcodecs_amd.lz4`.
 
 The 16-byte frame header is read on the host: version, versionlz, flags,
 typesize, then nbytes, blocksize, cbytes as little-endian u32.  For frames

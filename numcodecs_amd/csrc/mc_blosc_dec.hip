@@ -2,7 +2,8 @@
 // bytes on the device, for a whole batch of frames: one plan launch plus one
 // decode launch.  The frame and LZ4 rules, the sequence parser, the validity
 // predicate and the plan walker live in mc_lz4.h (compiled for the host too,
-// tests/native_lz4).  The inverse shuffle is mc_blosc_filter's job.
+// tests/native_lz4); the wave-wide sequence loop (decode_wave) is
+// mc_lz4_wave.h's.  The inverse shuffle is mc_blosc_filter's job.
 //
 // plan:   one thread per Blosc block of the batch; writes one mc_lz4_stream
 //         descriptor per stream, everything validated against the frame length.
@@ -23,13 +24,11 @@
 //         the match began.
 #include "mc_common.h"
 #include "mc_lz4.h"
+#include "mc_lz4_wave.h"  // decode_wave: the sequence loop, shared with mc_lz4_codec.hip
 
 namespace {
 
-constexpr uint32_t WAVE = 64;
-constexpr uint32_t RING_MAX = 65536;
-
-MC_DEV uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+using namespace mc_lz4w;
 
 MC_DEV void record_error(int32_t *err, uint32_t frame, int code, uint32_t stream) {
   // first error of a frame wins; plain vector atomics / stores
@@ -54,40 +53,6 @@ plan_kernel(const uint8_t *__restrict__ frames, const mc_blosc_frame *__restrict
   if (e != MC_LZ4_OK) record_error(err, lo, e, bad);
 }
 
-// Orders this wave's LDS writes before its later LDS reads: the LDS executes
-// one wave's instructions in issue order, the wait makes them complete, and
-// the "memory" clobber keeps the compiler from moving an access across.
-// (A workgroup barrier orders them too; its fence also waits for the streamed
-// global stores, which nothing here needs.  Measured the same on MI355X.)
-MC_DEV void lds_order() { __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// the source stream through a 64-byte window held one byte per lane; the 64
-// bytes after it are loaded ahead, so that a refill seldom waits for memory
-struct wave_reader {
-  const uint8_t *src;
-  uint32_t n, base, lane;
-  uint32_t w, ahead;
-  MC_DEV uint32_t load(uint32_t at) { return (at + lane < n) ? src[at + lane] : 0u; }  // at <= n < 2^31
-  MC_DEV void start() {
-    base = 0;
-    w = load(0);
-    ahead = load(WAVE < n ? WAVE : n);
-  }
-  MC_DEV uint32_t byte(uint32_t i) {
-    if (i - base >= WAVE) {  // wave-uniform: i and base are
-      if (i - base < 2 * WAVE) {
-        base += WAVE;
-        w = ahead;
-      } else {
-        base = i;
-        w = load(i);
-      }
-      ahead = load(n - base > WAVE ? base + WAVE : n);
-    }
-    return (uint32_t)__builtin_amdgcn_readlane((int)w, (int)uni(i - base));
-  }
-};
-
 __global__ void __launch_bounds__(WAVE)
 decode_kernel(const uint8_t *__restrict__ frames, const mc_lz4_stream *__restrict__ streams, uint32_t nstreams,
               uint32_t ring_mask, int32_t *__restrict__ err) {
@@ -103,80 +68,9 @@ decode_kernel(const uint8_t *__restrict__ frames, const mc_lz4_stream *__restric
     for (uint32_t k = lane; k < usize; k += WAVE) dst[k] = src[k];
     return;
   }
-  wave_reader rd{src, n, 0u, lane, 0u, 0u};
-  rd.start();
-  uint32_t ip = 0, op = 0;
-  int e = MC_LZ4_OK;
-  while (ip < n) {
-    mc_lz4_seq s;
-    e = mc_lz4_parse(rd, n, ip, &s);
-    if (e == MC_LZ4_OK) e = mc_lz4_check(s, op, usize);
-    e = (int)uni((uint32_t)e);
-    if (e != MC_LZ4_OK) break;  // nothing of the sequence is copied
-    const uint32_t lit_pos = uni(s.lit_pos), lit_len = uni(s.lit_len);
-    const uint32_t offset = uni(s.offset), match_len = uni(s.match_len);
-    // literals: source -> ring + global; a short run that the window still
-    // holds comes out of its registers (no memory latency on the chain)
-    if (lit_len && lit_pos >= rd.base && lit_pos - rd.base + lit_len <= WAVE) {
-      const uint8_t v = (uint8_t)__shfl(rd.w, (int)((lit_pos - rd.base + lane) & (WAVE - 1)), WAVE);
-      if (lane < lit_len) {
-        ring[(op + lane) & ring_mask] = v;
-        dst[op + lane] = v;
-      }
-    } else {
-      for (uint32_t k = 0; k < lit_len; k += WAVE) {
-        const uint32_t i = k + lane;
-        if (i < lit_len) {
-          const uint8_t v = src[lit_pos + i];
-          ring[(op + i) & ring_mask] = v;
-          dst[op + i] = v;
-        }
-      }
-    }
-    op += lit_len;
-    if (lit_len) lds_order();
-    // match: ring -> ring + global
-    if (offset >= WAVE) {
-      // 64 bytes a step: a step reads only bytes of earlier steps (offset >= 64)
-      for (uint32_t k = 0; k < match_len; k += WAVE) {
-        const uint32_t i = k + lane;
-        if (i < match_len) {
-          const uint8_t v = ring[(op + i - offset) & ring_mask];
-          ring[(op + i) & ring_mask] = v;
-          dst[op + i] = v;
-        }
-        lds_order();
-      }
-    } else if (match_len) {
-      // replicating form: only the `offset` bytes before the match are read
-      // (lane p < offset keeps byte p of them; a long match may wrap the ring
-      // over them, so they are read once, before anything is written)
-      uint32_t ph = lane % offset;  // (k + lane) % offset
-      const uint32_t step = WAVE % offset;
-      const uint32_t pat = ring[(op - offset + ph) & ring_mask];
-      for (uint32_t k = 0; k < match_len; k += WAVE) {
-        const uint32_t i = k + lane;
-        const uint8_t v = (uint8_t)__shfl(pat, (int)ph, WAVE);
-        if (i < match_len) {
-          ring[(op + i) & ring_mask] = v;
-          dst[op + i] = v;
-        }
-        ph += step;
-        if (ph >= offset) ph -= offset;
-      }
-      lds_order();
-    }
-    op += match_len;
-    ip = uni(s.next);
-  }
-  if (e == MC_LZ4_OK && op != usize) e = MC_LZ4_E_SIZE;
+  uint32_t produced;
+  const int e = decode_wave(src, n, dst, usize, ring, ring_mask, lane, &produced);
   if (e != MC_LZ4_OK && lane == 0) record_error(err, d.frame, e, sidx);
-}
-
-uint32_t ring_bytes(size_t max_stream) {
-  uint32_t r = 256;
-  while (r < max_stream && r < RING_MAX) r <<= 1;
-  return r;
 }
 
 }  // namespace

@@ -2,7 +2,8 @@
 // device, for a whole batch of frames: three launches.  The match-finding and
 // emission rules, the scalar encoder they are checked against and the frame
 // layout helpers live in mc_lz4_enc.h (compiled for the host too,
-// tests/native_lz4enc).  The forward shuffle is mc_blosc_filter's job.
+// tests/native_lz4enc); the wave-wide match finder (encode_wave) is
+// mc_lz4_wave.h's.  The forward shuffle is mc_blosc_filter's job.
 //
 // compress: one wave (a 64-lane workgroup) per stream, wave-uniform control
 //           flow.  The source is read-only, so candidate words and match
@@ -22,18 +23,11 @@
 //           slot; for a memcpyed frame its share of the unfiltered input.
 #include "mc_common.h"
 #include "mc_lz4_enc.h"
+#include "mc_lz4_wave.h"  // encode_wave: the match finder, shared with mc_lz4_codec.hip
 
 namespace {
 
-constexpr uint32_t WAVE = 64;
-
-MC_DEV uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-// see mc_blosc_dec.hip: orders this wave's LDS accesses across the call
-MC_DEV void lds_order() { __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-MC_DEV uint32_t ld_le32(const uint8_t *p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
+using namespace mc_lz4w;
 
 // the frame whose [stream_base, next stream_base) holds stream s
 MC_DEV uint32_t frame_of_stream(const mc_blosc_enc_frame *table, uint32_t nframes, uint32_t s) {
@@ -43,110 +37,6 @@ MC_DEV uint32_t frame_of_stream(const mc_blosc_enc_frame *table, uint32_t nframe
     if (table[mid].stream_base <= s) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-// first lane whose predicate is false, 64 if none
-MC_DEV uint32_t first_false(bool pred) {
-  const uint64_t ne = ~__ballot(pred);
-  return ne ? (uint32_t)__ffsll((long long)ne) - 1u : WAVE;
-}
-
-// length v's extension run at dst, by all lanes
-MC_DEV void put_ext(uint8_t *dst, uint32_t v, uint32_t count, uint32_t lane) {
-  for (uint32_t k = lane; k < count; k += WAVE) dst[k] = mc_lz4e_ext_byte(v, count, k);
-}
-
-// n source bytes -> at most cap bytes at dst; the compressed size or 0 (raw).
-// Same bytes as mc_lz4_encode_stream.  Reads src[0, n) and writes dst[0, cap) only.
-MC_DEV uint32_t encode_wave(const uint8_t *__restrict__ src, uint32_t n, uint8_t *__restrict__ dst, uint32_t cap,
-                            uint32_t *tbl, uint32_t lane) {
-  if (n < MC_LZ4E_MINLEN || n >= MC_LZ4_MAX_USIZE) return 0;
-  for (uint32_t k = 4 * lane; k < MC_LZ4E_TABLE; k += 4 * WAVE)
-    *reinterpret_cast<mc_u32x4 *>(tbl + k) = mc_u32x4{0u, 0u, 0u, 0u};
-  lds_order();
-  const uint32_t mflimit = n - MC_LZ4E_MFLIMIT, matchlimit = n - MC_LZ4E_LASTLITS;
-  uint32_t p = 0, anchor = 0, op = 0;
-  while (p < mflimit) {
-    // the window's 67 bytes staged one per lane (+3 in lanes 0-2); every
-    // lane's word is put together from its neighbours' registers
-    const uint32_t pos = p + lane;
-    const uint32_t b0 = pos < n ? src[pos] : 0u;
-    const uint32_t b1 = (lane < 3 && n - p > WAVE + lane) ? src[p + WAVE + lane] : 0u;
-    uint32_t w = b0;
-#pragma unroll
-    for (uint32_t k = 1; k < 4; ++k) {
-      const uint32_t idx = lane + k;
-      const uint32_t v = (uint32_t)__shfl((int)b0, (int)(idx & (WAVE - 1)), WAVE);
-      const uint32_t t = (uint32_t)__shfl((int)b1, (int)(idx & (WAVE - 1)), WAVE);
-      w |= (idx < WAVE ? v : t) << (8 * k);
-    }
-    const bool active = pos < mflimit;
-    const uint32_t h = mc_lz4e_hash(w);
-    const uint32_t entry = active ? tbl[h] : 0u;
-    const uint32_t cand = entry - 1;
-    bool ok = mc_lz4e_entry_ok(entry, pos);
-    if (ok) ok = ld_le32(src + cand) == w;  // cand + 3 < pos + 3 < n
-    const uint64_t hit = __ballot(ok);
-    if (hit == 0) {
-      if (active) atomicMax(&tbl[h], pos + 1);
-      lds_order();
-      p += WAVE;
-      continue;
-    }
-    const uint32_t win = uni((uint32_t)__ffsll((long long)hit) - 1u);
-    uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)pos, (int)win);
-    uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cand, (int)win);
-    // backwards: at most min(m - anchor, c) bytes; forwards: the slot's 4
-    // bytes are known equal, up to n - 5.  64 bytes a step; the first step of
-    // both directions is one round of loads (neither depends on the other)
-    const uint32_t maxback = m - anchor < c ? m - anchor : c;
-    const bool beq = lane < maxback && src[m - 1 - lane] == src[c - 1 - lane];
-    const bool feq = 4 + lane < matchlimit - m && src[c + 4 + lane] == src[m + 4 + lane];
-    uint32_t back = first_false(beq), fwd = 4 + first_false(feq);
-    while (back % WAVE == 0 && back) {  // every byte of the last step was equal
-      const uint32_t i = back + lane;
-      const uint32_t f = first_false(i < maxback && src[m - 1 - i] == src[c - 1 - i]);
-      back += f;
-      if (f < WAVE) break;
-    }
-    while ((fwd - 4) % WAVE == 0 && fwd > 4) {
-      const uint32_t i = fwd + lane;
-      const uint32_t f = first_false(i < matchlimit - m && src[c + i] == src[m + i]);
-      fwd += f;
-      if (f < WAVE) break;
-    }
-    m -= back, c -= back;
-    const uint32_t len = uni(back + fwd);
-    m = uni(m), c = uni(c);
-    const uint32_t lit = m - anchor, mend = m + len;
-    if (mc_lz4e_seq_bytes(lit, len) > cap - op) return 0;  // checked before any byte of the sequence
-    const uint32_t nle = mc_lz4e_ext_count(lit), nme = mc_lz4e_ext_count(len - 4);
-    if (lane == 0) dst[op] = mc_lz4e_token(lit, len - 4);
-    uint8_t *q = dst + op + 1;
-    put_ext(q, lit, nle, lane);
-    q += nle;
-    for (uint32_t k = lane; k < lit; k += WAVE) q[k] = src[anchor + k];
-    q += lit;
-    if (lane < 2) q[lane] = (uint8_t)((m - c) >> (8 * lane));
-    q += 2;
-    put_ext(q, len - 4, nme, lane);
-    op += 1 + nle + lit + 2 + nme;
-    // only the positions consumed from this window enter the table
-    const uint32_t lim = mend - p < WAVE ? mend : p + WAVE;
-    if (active && pos < lim) atomicMax(&tbl[h], pos + 1);
-    lds_order();
-    p = anchor = mend;
-  }
-  const uint32_t lit = n - anchor;
-  if (mc_lz4e_last_bytes(lit) > cap - op) return 0;
-  const uint32_t nle = mc_lz4e_ext_count(lit);
-  if (lane == 0) dst[op] = mc_lz4e_token(lit, 0);
-  uint8_t *q = dst + op + 1;
-  put_ext(q, lit, nle, lane);
-  q += nle;
-  for (uint32_t k = lane; k < lit; k += WAVE) q[k] = src[anchor + k];
-  op += 1 + nle + lit;
-  return op < n ? op : 0;
 }
 
 struct enc_args {
@@ -175,7 +65,8 @@ __global__ void __launch_bounds__(WAVE) compress_kernel(enc_args a) {
     const uint8_t *src = reinterpret_cast<const uint8_t *>((uintptr_t)(a.base + f.src)) + off;
     uint8_t *dst = a.scratch + f.scratch_off + off;
     neb = uni(neb);
-    out = encode_wave(mc_uniform_ptr(src), neb, mc_uniform_ptr(dst), neb, tbl, lane);
+    mc_lz4e_marks marks;  // a stitching caller's; unused here
+    out = encode_wave(mc_uniform_ptr(src), neb, mc_uniform_ptr(dst), neb, tbl, lane, &marks);
   }
   if (lane == 0) a.csize[sidx] = out;
 }

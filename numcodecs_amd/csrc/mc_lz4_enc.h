@@ -68,9 +68,18 @@ MC_LZ4_HD uint32_t mc_lz4e_seq_bytes(uint32_t lit, uint32_t ml) {
 }
 MC_LZ4_HD uint32_t mc_lz4e_last_bytes(uint32_t lit) { return 1 + mc_lz4e_ext_count(lit) + lit; }
 
+// What a caller that stitches streams needs to know of one (mc_lz4_codec.h);
+// set when the encoder returns non-zero.
+struct mc_lz4e_marks {
+  uint32_t first_lit;  // literal length of the first sequence
+  uint32_t close_at;   // offset of the closing (literal-only) sequence's token in dst
+  uint32_t tail_lit;   // its literal length
+};
+
 // The scalar encoder (host): n source bytes into at most cap bytes at dst.
 // Returns the compressed size, or 0 when the stream is to be stored raw.
-static inline uint32_t mc_lz4_encode_stream(const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap) {
+static inline uint32_t mc_lz4_encode_stream_marks(const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap,
+                                                  mc_lz4e_marks *marks) {
   if (n < MC_LZ4E_MINLEN || n >= MC_LZ4_MAX_USIZE) return 0;
   uint32_t table[MC_LZ4E_TABLE];
   for (uint32_t i = 0; i < MC_LZ4E_TABLE; ++i) table[i] = 0;
@@ -94,6 +103,7 @@ static inline uint32_t mc_lz4_encode_stream(const uint8_t *src, uint32_t n, uint
       // backward-extended match: the loop runs over them again)
       const uint32_t lit = m - anchor, need = mc_lz4e_seq_bytes(lit, ml);
       if (need > cap - op) return 0;
+      if (op == 0) marks->first_lit = lit;
       dst[op++] = mc_lz4e_token(lit, ml - 4);
       const uint32_t nle = mc_lz4e_ext_count(lit), nme = mc_lz4e_ext_count(ml - 4);
       for (uint32_t k = 0; k < nle; ++k) dst[op++] = mc_lz4e_ext_byte(lit, nle, k);
@@ -110,11 +120,16 @@ static inline uint32_t mc_lz4_encode_stream(const uint8_t *src, uint32_t n, uint
   }
   const uint32_t lit = n - anchor, need = mc_lz4e_last_bytes(lit);
   if (need > cap - op) return 0;
+  marks->close_at = op, marks->tail_lit = lit;
   dst[op++] = mc_lz4e_token(lit, 0);
   const uint32_t nle = mc_lz4e_ext_count(lit);
   for (uint32_t k = 0; k < nle; ++k) dst[op++] = mc_lz4e_ext_byte(lit, nle, k);
   for (uint32_t k = 0; k < lit; ++k) dst[op++] = src[anchor + k];
   return op < n ? op : 0;
+}
+static inline uint32_t mc_lz4_encode_stream(const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap) {
+  mc_lz4e_marks marks;
+  return mc_lz4_encode_stream_marks(src, n, dst, cap, &marks);
 }
 
 // ---------------------------------------------------------------------------
