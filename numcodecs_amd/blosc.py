@@ -26,16 +26,19 @@ decompression: -1')``, the reference's text with c-blosc's generic code.
 
 ``Blosc`` is the decode-only class (its ``encode`` raises); ``BloscLZ4`` is
 the full codec.  Neither is registered on import: call :func:`register`.
+
+Staging a batch's inputs, placing its outputs and handing results back is
+:mod:`numcodecs_amd._frames`, shared with the ``lz4`` codec; the rest is Blosc's.
 """
 
 import numpy as np
 import torch
 
-from . import _native
+from . import _frames
 from ._native import check, lib
 from .abc import Codec
 from .blosc_shuffle import AUTOBLOCKS, AUTOSHUFFLE, BITSHUFFLE, NOSHUFFLE, SHUFFLE
-from .compat import device_out, download, ensure_contiguous_ndarray, is_device_tensor, upload
+from .compat import ensure_contiguous_ndarray, is_device_tensor, upload
 from .registry import register_codec
 
 __all__ = ["Blosc", "BloscLZ4", "NOSHUFFLE", "SHUFFLE", "BITSHUFFLE", "AUTOSHUFFLE", "AUTOBLOCKS", "cbuffer_sizes",
@@ -47,7 +50,6 @@ _FORMAT_LZ4 = 1
 _FORMAT_NAMES = {0: "blosclz", 1: "lz4", 2: "snappy", 3: "zlib", 4: "zstd"}
 _MAX_BLOCKSIZE = (1 << 30) - 1  # mc_blosc_decode_batch refuses more (c-blosc's own limit is lower)
 _ERROR_TEXT = "error during blosc decompression: -1"
-_ALIGN = 256
 
 # one record of mc_blosc_decode_batch's frame table (include/mcodec.h)
 _FRAME_RECORD = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst", "<u8"), ("nbytes", "<u4"),
@@ -73,12 +75,8 @@ def _parse_header(hdr) -> tuple:
 
 
 def _flat_bytes(buf):
-    """`buf` as flat uint8: a device tensor stays one, anything else becomes a
-    numpy view (ensure_contiguous_ndarray semantics, blosc.pyx:499)."""
-    arr = ensure_contiguous_ndarray(buf, Blosc.max_buffer_size)
-    if is_device_tensor(arr):
-        return arr.view(torch.uint8) if arr.numel() else arr.new_empty(0, dtype=torch.uint8)
-    return arr.view(np.uint8)
+    """`buf` as flat uint8 (blosc.pyx:499), within ``Blosc.max_buffer_size``."""
+    return _frames.flat_bytes(buf, Blosc.max_buffer_size)
 
 
 def cbuffer_sizes(source):
@@ -106,20 +104,13 @@ def _nstreams(flags, typesize, nbytes, blocksize):
     return nblocks, full * typesize + (nblocks - full), longest
 
 
-def _out_bytes(out, nbytes):
-    """A caller's `out` as flat uint8 (device tensor or numpy), size-checked."""
-    flat = ensure_contiguous_ndarray(device_out(out))
-    if is_device_tensor(flat):
-        raw = flat.view(torch.uint8) if flat.numel() else flat.new_empty(0, dtype=torch.uint8)
-        have = raw.numel()
-    else:
-        if not flat.flags.writeable:
-            raise ValueError("destination buffer is read-only")
-        raw = flat.view(np.uint8)
-        have = raw.nbytes
-    if have < nbytes:
-        raise ValueError("destination buffer too small; expected at least %s, got %s" % (nbytes, have))
-    return raw
+def _mode(flags, typesize):
+    """The filter a frame's bytes still carry once its streams are decoded."""
+    if flags & _F_MEMCPYED:
+        return NOSHUFFLE
+    if flags & _F_BITSHUFFLE:
+        return BITSHUFFLE
+    return SHUFFLE if flags & _F_SHUFFLE and typesize > 1 else NOSHUFFLE
 
 
 def decompress_many(frames, outs=None):
@@ -141,39 +132,12 @@ def decompress_many(frames, outs=None):
         return []
     srcs = [_flat_bytes(f) for f in frames]
     on_dev = [is_device_tensor(s) for s in srcs]
-    device = next((s.device for s, d in zip(srcs, on_dev) if d), None)
-    for o in outs:
-        if device is None and o is not None and is_device_tensor(device_out(o)):
-            device = device_out(o).device
-    if any(d and s.device != device for s, d in zip(srcs, on_dev)):
-        raise ValueError("all frames of a batch must be on one device")
-
-    # ---- the frames' bytes as one device buffer, and their offsets in it ----
+    device = _frames.batch_device(srcs, on_dev, outs, "frames")
     lengths = [int(len(s)) for s in srcs]
-    offsets = [0] * nf
-    pieces, pos = [], 0
-    host_idx = [i for i in range(nf) if not on_dev[i]]
-    if host_idx:
-        for i in host_idx:
-            offsets[i] = pos
-            pos += lengths[i]
-    for i in range(nf):
-        if on_dev[i]:
-            offsets[i] = pos
-            pos += lengths[i]
-
-    # ---- headers: host frames directly, device frames by one gathered copy ----
-    headers = [None] * nf
     short = {i: (-1, 0) for i in range(nf) if lengths[i] < _HEADER}
     if short:
         raise _decode_error(short)
-    for i in host_idx:
-        headers[i] = _parse_header(srcs[i][:_HEADER])
-    dev_idx = [i for i in range(nf) if on_dev[i]]
-    if dev_idx:
-        heads = torch.cat([srcs[i][:_HEADER] for i in dev_idx]).cpu().numpy().reshape(-1, _HEADER)
-        for k, i in enumerate(dev_idx):
-            headers[i] = _parse_header(heads[k])
+    headers = [_parse_header(h) for h in _frames.read_prefixes(srcs, on_dev, _HEADER)]
 
     # ---- host checks (before anything is launched) ----
     bad, unsupported = {}, None
@@ -189,58 +153,28 @@ def decompress_many(frames, outs=None):
         name = _FORMAT_NAMES.get(unsupported, f"format {unsupported}")
         raise NotImplementedError(f"Blosc frames compressed with {name!r} are not decoded on the GPU "
                                   "(only lz4 / lz4hc and memcpyed frames are)")
-    out_raw = [None if o is None else _out_bytes(o, headers[i][3]) for i, o in enumerate(outs)]
-    if any(is_device_tensor(o) and o.device != device for o in out_raw if o is not None) and device is not None:
-        raise ValueError("out must be on the same device as the frames")
+    sizes = [h[3] for h in headers]
+    out_raw = [None if o is None else _frames.out_bytes(o, sizes[i]) for i, o in enumerate(outs)]
+    _frames.check_out_device(out_raw, device)
 
-    live = [i for i in range(nf) if headers[i][3] > 0]
+    live = [i for i in range(nf) if sizes[i] > 0]
     results = [None] * nf
     for i in range(nf):
-        if headers[i][3] == 0:  # nothing to decode: no launch
+        if sizes[i] == 0:  # nothing to decode: no launch
             if out_raw[i] is not None:
                 results[i] = outs[i]
-            elif on_dev[i]:
-                results[i] = torch.empty(0, dtype=torch.uint8, device=device)
             else:
-                results[i] = np.empty(0, dtype=np.uint8)
+                results[i] = torch.empty(0, dtype=torch.uint8, device=device) if on_dev[i] else np.empty(0, np.uint8)
     if not live:
         return results
 
-    _native.require_device()
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    from ._ops import _guard, stream
-
-    with _guard(torch.empty(0, dtype=torch.uint8, device=device)):
-        if host_idx:
-            blob = np.concatenate([srcs[i] for i in host_idx]) if len(host_idx) > 1 else srcs[host_idx[0]]
-            pieces.append(upload(np.ascontiguousarray(blob), device))
-        pieces.extend(srcs[i] for i in dev_idx)
-        src_all = pieces[0] if len(pieces) == 1 else torch.cat(pieces)
-
-        # ---- where each frame's bytes go: its final place, and -- for frames
-        # that still need the inverse shuffle -- a temporary before that
-        def _mode(flags, typesize):
-            if flags & _F_MEMCPYED:
-                return NOSHUFFLE
-            if flags & _F_BITSHUFFLE:
-                return BITSHUFFLE
-            return SHUFFLE if flags & _F_SHUFFLE and typesize > 1 else NOSHUFFLE
-
-        own_off, own_total, tmp_off, tmp_total = {}, 0, {}, 0
-        for i in live:
-            nbytes = headers[i][3]
-            if not is_device_tensor(out_raw[i]):
-                own_off[i] = own_total
-                own_total += -(-nbytes // _ALIGN) * _ALIGN
-            if _mode(headers[i][1], headers[i][2]) != NOSHUFFLE:
-                tmp_off[i] = tmp_total
-                tmp_total += -(-nbytes // _ALIGN) * _ALIGN
-        own = torch.empty(own_total, dtype=torch.uint8, device=device)
+    with _frames.launching(device) as (device, st):
+        src_all, offsets = _frames.stage_packed(srcs, lengths, on_dev, device)
+        own, own_off, final = _frames.place(live, sizes, out_raw, device)
+        # frames that still need the inverse shuffle decode into a temporary first
+        shuffled = [i for i in live if _mode(headers[i][1], headers[i][2]) != NOSHUFFLE]
+        tmp_off, tmp_total = _frames.slot_map(shuffled, [sizes[i] for i in shuffled])
         tmp = torch.empty(tmp_total, dtype=torch.uint8, device=device)
-        final = {i: (own[own_off[i]:own_off[i] + headers[i][3]] if i in own_off else out_raw[i][:headers[i][3]])
-                 for i in live}
-
         table = np.zeros(len(live), dtype=_FRAME_RECORD)
         nblocks = nstreams = longest = 0
         for k, i in enumerate(live):
@@ -255,30 +189,17 @@ def decompress_many(frames, outs=None):
         ws_bytes = lib.mc_blosc_decode_workspace(nstreams)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         err = torch.empty(2 * len(live), dtype=torch.int32, device=device)
-        st = stream(src_all)
         check(lib.mc_blosc_decode_batch(src_all.data_ptr(), table_d.data_ptr(), len(live), nblocks, nstreams,
                                         longest, ws.data_ptr(), ws_bytes, err.data_ptr(), st),
               "mc_blosc_decode_batch")
-        for i in tmp_off:  # one unshuffle launch per frame (a known limit: DESIGN.md §6b)
+        for i in shuffled:  # one unshuffle launch per frame (a known limit: DESIGN.md §6b)
             _v, flags, typesize, nbytes, blocksize, _c = headers[i]
-            check(lib.mc_blosc_filter(tmp.data_ptr() + tmp_off[i], final[i].data_ptr(), nbytes, typesize, blocksize,
-                                      _mode(flags, typesize), 0, st), "mc_blosc_filter")
+            check(lib.mc_blosc_filter(tmp.data_ptr() + tmp_off[i], final[i].data_ptr(), nbytes, typesize,
+                                      blocksize, _mode(flags, typesize), 0, st), "mc_blosc_filter")
         codes = err.cpu().numpy().reshape(-1, 2)  # waits for the stream
         if codes[:, 0].any():
             raise _decode_error({live[k]: (int(c), int(s)) for k, (c, s) in enumerate(codes) if c})
-        host_all = download(own) if any(not on_dev[i] or isinstance(out_raw[i], np.ndarray) for i in own_off) \
-            else None
-        for i in live:
-            nbytes = headers[i][3]
-            if is_device_tensor(out_raw[i]):
-                results[i] = outs[i]
-            elif out_raw[i] is not None:  # a host destination
-                out_raw[i][:nbytes] = host_all[own_off[i]:own_off[i] + nbytes]
-                results[i] = outs[i]
-            elif on_dev[i]:
-                results[i] = final[i]
-            else:
-                results[i] = host_all[own_off[i]:own_off[i] + nbytes]
+        _frames.hand_back(results, own, own_off, final, live, sizes, outs, out_raw, on_dev)
     return results
 
 
@@ -415,9 +336,7 @@ def compress_many(sources, cname="lz4", clevel=5, shuffle=SHUFFLE, blocksize=AUT
         srcs.append(flat)
         params.append(_frame_params(int(len(flat)), itemsize, clevel, mode, blocksize))
     on_dev = [is_device_tensor(s) for s in srcs]
-    device = next((s.device for s, d in zip(srcs, on_dev) if d), None)
-    if any(d and s.device != device for s, d in zip(srcs, on_dev)):
-        raise ValueError("all buffers of a batch must be on one device")
+    device = _frames.batch_device(srcs, on_dev, what="buffers")
     lengths = [int(len(s)) for s in srcs]
     if any(p[1] > _MAX_BLOCKSIZE for p in params):
         raise ValueError("Blosc block sizes of 2**30 bytes and above are not supported")
@@ -432,40 +351,16 @@ def compress_many(sources, cname="lz4", clevel=5, shuffle=SHUFFLE, blocksize=AUT
     if not live:
         return results
 
-    _native.require_device()
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    from ._ops import _guard, stream
-
-    with _guard(torch.empty(0, dtype=torch.uint8, device=device)):
-        # ---- the inputs on the device: host buffers by one upload ----
-        host_idx = [i for i in live if not on_dev[i]]
-        raw = {i: srcs[i] for i in live if on_dev[i]}
-        if host_idx:
-            offs = np.cumsum([0] + [-(-lengths[i] // _ALIGN) * _ALIGN for i in host_idx])
-            blob = np.zeros(int(offs[-1]), np.uint8)
-            for k, i in enumerate(host_idx):
-                blob[offs[k]:offs[k] + lengths[i]] = srcs[i]
-            blob_d = upload(blob, device)
-            for k, i in enumerate(host_idx):
-                raw[i] = blob_d[int(offs[k]):int(offs[k]) + lengths[i]]
-
-        # ---- slots: the output (nbytes + 16 each), the filtered copy of a
-        # shuffled frame, and the compress kernel's scratch (nbytes each)
-        def _up(n):
-            return -(-n // _ALIGN) * _ALIGN
-
-        out_off, tmp_off, scr_off = {}, {}, {}
-        out_total = tmp_total = scr_total = 0
-        for i in live:
-            out_off[i], out_total = out_total, out_total + _up(lengths[i] + _MAX_OVERHEAD)
-            if params[i][3] != NOSHUFFLE:
-                tmp_off[i], tmp_total = tmp_total, tmp_total + _up(lengths[i])
-            if not params[i][0] & _F_MEMCPYED:
-                scr_off[i], scr_total = scr_total, scr_total + _up(lengths[i])
+    with _frames.launching(device) as (device, st):
+        raw = _frames.stage_aligned(srcs, live, on_dev, device)
+        # slots: the output (nbytes + 16), a shuffled frame's filtered copy and the compress kernel's scratch (nbytes)
+        out_off, out_total = _frames.slot_map(live, [lengths[i] + _MAX_OVERHEAD for i in live])
+        shuffled = [i for i in live if params[i][3] != NOSHUFFLE]
+        tmp_off, tmp_total = _frames.slot_map(shuffled, [lengths[i] for i in shuffled])
+        packed = [i for i in live if not params[i][0] & _F_MEMCPYED]
+        scr_off, scr_total = _frames.slot_map(packed, [lengths[i] for i in packed])
         out = torch.empty(out_total, dtype=torch.uint8, device=device)
         tmp = torch.empty(tmp_total, dtype=torch.uint8, device=device)
-        st = stream(out)
         table = np.zeros(len(live), dtype=_ENC_RECORD)
         nblocks = nstreams = 0
         for k, i in enumerate(live):
@@ -487,14 +382,11 @@ def compress_many(sources, cname="lz4", clevel=5, shuffle=SHUFFLE, blocksize=AUT
         cbytes_d = torch.empty(len(live), dtype=torch.int32, device=device)
         check(lib.mc_blosc_encode_batch(None, table_d.data_ptr(), len(live), nblocks, nstreams, ws.data_ptr(),
                                         ws_bytes, cbytes_d.data_ptr(), st), "mc_blosc_encode_batch")
-        cbytes = cbytes_d.cpu().numpy().view(np.uint32)  # waits for the stream
+        cbytes = cbytes_d.cpu().numpy().view(np.uint32).tolist()  # waits for the stream
         for k, i in enumerate(live):
             if not _HEADER < cbytes[k] <= lengths[i] + _MAX_OVERHEAD:
                 raise RuntimeError("error during blosc compression: %d" % (cbytes[k] if cbytes[k] else -1))
-        host_all = download(out) if host_idx else None
-        for k, i in enumerate(live):
-            lo, hi = out_off[i], out_off[i] + int(cbytes[k])
-            results[i] = out[lo:hi] if on_dev[i] else host_all[lo:hi]
+        _frames.hand_back_encoded(results, out, out_off, cbytes, live, on_dev)
     return results
 
 

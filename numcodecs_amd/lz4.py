@@ -26,16 +26,18 @@ what the decoder here cannot read.  ``LZ4.max_buffer_size`` keeps the
 reference's value.
 
 The codec is not registered on import: call :func:`register`.
+
+Staging a batch's inputs, placing its outputs and handing results back is
+:mod:`numcodecs_amd._frames`, shared with Blosc; the rest is the codec's own.
 """
 
 import numpy as np
 import torch
 
-from . import _native
+from . import _frames
 from ._native import check, lib
 from .abc import Codec
-from .blosc import _out_bytes
-from .compat import device_out, download, ensure_contiguous_ndarray, is_device_tensor, upload
+from .compat import is_device_tensor, upload
 from .registry import register_codec
 
 __all__ = ["LZ4", "DEFAULT_ACCELERATION", "compress", "compress_many", "decompress", "decompress_many", "register"]
@@ -44,7 +46,6 @@ DEFAULT_ACCELERATION = 1
 _HEADER = 4
 _MAX_CHUNK = 1 << 30  # csrc/mc_lz4.h MC_LZ4_MAX_USIZE: the device decoder's streams are shorter
 _SEGMENT = 65536      # csrc/mc_lz4_codec.h MC_LZ4C_SEGMENT
-_ALIGN = 256
 _EMPTY_FRAME = bytes(5)
 _E_SIZE = 10          # csrc/mc_lz4.h MC_LZ4_E_SIZE: the block ended short of the size word
 _E_TRUNCATED = 4      # MC_LZ4_E_TRUNCATED
@@ -56,22 +57,14 @@ _DEC_RECORD = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst", "<u8"), 
 assert _ENC_RECORD.itemsize == 40 and _DEC_RECORD.itemsize == 32
 
 
-def _up(n):
-    return -(-n // _ALIGN) * _ALIGN
-
-
 def _frame_slot(n):
     """The reference's destination size: 4 + LZ4_compressBound(n)."""
     return _HEADER + n + n // 255 + 16
 
 
 def _flat_bytes(buf):
-    """`buf` as flat uint8: a device tensor stays one, anything else becomes a
-    numpy view (ensure_contiguous_ndarray semantics, lz4.pyx:219)."""
-    arr = ensure_contiguous_ndarray(buf, LZ4.max_buffer_size)
-    if is_device_tensor(arr):
-        return arr.view(torch.uint8) if arr.numel() else arr.new_empty(0, dtype=torch.uint8)
-    return arr.view(np.uint8)
+    """`buf` as flat uint8 (lz4.pyx:219), within ``LZ4.max_buffer_size``."""
+    return _frames.flat_bytes(buf, LZ4.max_buffer_size)
 
 
 def _too_long(n):
@@ -99,9 +92,7 @@ def compress_many(sources, acceleration=DEFAULT_ACCELERATION):
     if nf == 0:
         return []
     on_dev = [is_device_tensor(s) for s in srcs]
-    device = next((s.device for s, d in zip(srcs, on_dev) if d), None)
-    if any(d and s.device != device for s, d in zip(srcs, on_dev)):
-        raise ValueError("all buffers of a batch must be on one device")
+    device = _frames.batch_device(srcs, on_dev, what="buffers")
     lengths = [int(len(s)) for s in srcs]
     for n in lengths:
         if n >= _MAX_CHUNK:
@@ -116,53 +107,32 @@ def compress_many(sources, acceleration=DEFAULT_ACCELERATION):
     if not live:
         return results
 
-    _native.require_device()
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    from ._ops import _guard, stream
-
-    with _guard(torch.empty(0, dtype=torch.uint8, device=device)):
-        # ---- the inputs on the device: host buffers by one upload ----
-        host_idx = [i for i in live if not on_dev[i]]
-        raw = {i: srcs[i] for i in live if on_dev[i]}
-        if host_idx:
-            offs = np.cumsum([0] + [_up(lengths[i]) for i in host_idx])
-            blob = np.zeros(int(offs[-1]), np.uint8)
-            for k, i in enumerate(host_idx):
-                blob[offs[k]:offs[k] + lengths[i]] = srcs[i]
-            blob_d = upload(blob, device)
-            for k, i in enumerate(host_idx):
-                raw[i] = blob_d[int(offs[k]):int(offs[k]) + lengths[i]]
-
+    with _frames.launching(device) as (device, st):
+        raw = _frames.stage_aligned(srcs, live, on_dev, device)
         # ---- slots: the frame (the reference's bound) and the scratch (nbytes) ----
+        out_off, out_total = _frames.slot_map(live, [_frame_slot(lengths[i]) for i in live])
+        scr_off, scr_total = _frames.slot_map(live, [lengths[i] for i in live])
         table = np.zeros(len(live), dtype=_ENC_RECORD)
-        out_off, out_total, scr_total, nsegs = {}, 0, 0, 0
+        nsegs = 0
         for k, i in enumerate(live):
             n = lengths[i]
-            out_off[i] = out_total
-            table[k] = (raw[i].data_ptr(), out_total, scr_total, n, _frame_slot(n), nsegs, 0)
-            out_total += _up(_frame_slot(n))
-            scr_total += _up(n)
+            table[k] = (raw[i].data_ptr(), out_off[i], scr_off[i], n, _frame_slot(n), nsegs, 0)
             nsegs += -(-n // _SEGMENT)
         if nsegs > 2**31 - 1:
             raise ValueError("too many LZ4 segments in one batch")
         out = torch.empty(out_total, dtype=torch.uint8, device=device)
         table["dst"] += out.data_ptr()
-        st = stream(out)
         table_d = upload(table.view(np.uint8), device)
         ws_bytes = lib.mc_lz4_encode_workspace(len(live), nsegs, scr_total)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         cbytes_d = torch.empty(len(live), dtype=torch.int32, device=device)
         check(lib.mc_lz4_encode_batch(None, table_d.data_ptr(), len(live), nsegs, ws.data_ptr(), ws_bytes,
                                       cbytes_d.data_ptr(), st), "mc_lz4_encode_batch")
-        cbytes = cbytes_d.cpu().numpy().view(np.uint32)  # waits for the stream
+        cbytes = cbytes_d.cpu().numpy().view(np.uint32).tolist()  # waits for the stream
         for k, i in enumerate(live):
             if not _HEADER < cbytes[k] <= _frame_slot(lengths[i]):
                 raise RuntimeError("LZ4 compression error: %d" % (cbytes[k] if cbytes[k] else -1))
-        host_all = download(out) if host_idx else None
-        for k, i in enumerate(live):
-            lo, hi = out_off[i], out_off[i] + int(cbytes[k])
-            results[i] = out[lo:hi] if on_dev[i] else host_all[lo:hi]
+        _frames.hand_back_encoded(results, out, out_off, cbytes, live, on_dev)
     return results
 
 
@@ -211,27 +181,12 @@ def decompress_many(frames, outs=None):
         return []
     srcs = [_flat_bytes(f) for f in frames]
     on_dev = [is_device_tensor(s) for s in srcs]
-    device = next((s.device for s, d in zip(srcs, on_dev) if d), None)
-    for o in outs:
-        if device is None and o is not None and is_device_tensor(device_out(o)):
-            device = device_out(o).device
-    if any(d and s.device != device for s, d in zip(srcs, on_dev)):
-        raise ValueError("all frames of a batch must be on one device")
+    device = _frames.batch_device(srcs, on_dev, outs, "frames")
     lengths = [int(len(s)) for s in srcs]
     short = {i: (-1, 0) for i in range(nf) if lengths[i] < _HEADER}
     if short:
         raise _decode_error("bad input data", short, ValueError)
-
-    # ---- size words: host frames directly, device frames by one gathered copy ----
-    host_idx = [i for i in range(nf) if not on_dev[i]]
-    dev_idx = [i for i in range(nf) if on_dev[i]]
-    sizes = [0] * nf
-    for i in host_idx:
-        sizes[i] = int.from_bytes(bytes(srcs[i][:_HEADER]), "little", signed=True)
-    if dev_idx:
-        words = torch.cat([srcs[i][:_HEADER] for i in dev_idx]).cpu().numpy().view("<i4")
-        for k, i in enumerate(dev_idx):
-            sizes[i] = int(words[k])
+    sizes = _frames.read_prefixes(srcs, on_dev, _HEADER).view("<i4").ravel().tolist()
 
     # ---- host checks (before anything is launched) ----
     bad = {i: (-1, 0) for i in range(nf) if sizes[i] <= 0}
@@ -240,45 +195,24 @@ def decompress_many(frames, outs=None):
     bad = {i: (_E_TRUNCATED, 0) for i in range(nf) if lengths[i] == _HEADER}  # no block at all
     if bad:
         raise _decode_error(_device_error_text(_E_TRUNCATED, 0, 0), bad)
-    out_raw = [None if o is None else _out_bytes(o, sizes[i]) for i, o in enumerate(outs)]
+    out_raw = [None if o is None else _frames.out_bytes(o, sizes[i]) for i, o in enumerate(outs)]
     for n in sizes:
         if n >= _MAX_CHUNK:
             raise _too_long(n)
-    if any(is_device_tensor(o) and o.device != device for o in out_raw if o is not None) and device is not None:
-        raise ValueError("out must be on the same device as the frames")
+    _frames.check_out_device(out_raw, device)
 
-    _native.require_device()
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    from ._ops import _guard, stream
-
-    with _guard(torch.empty(0, dtype=torch.uint8, device=device)):
-        # ---- the frames' bytes as one device buffer: host frames by one upload ----
-        offsets, pieces, pos = [0] * nf, [], 0
-        for i in host_idx + dev_idx:
-            offsets[i] = pos
-            pos += lengths[i]
-        if host_idx:
-            blob = np.concatenate([srcs[i] for i in host_idx]) if len(host_idx) > 1 else srcs[host_idx[0]]
-            pieces.append(upload(np.ascontiguousarray(blob), device))
-        pieces.extend(srcs[i] for i in dev_idx)
-        src_all = pieces[0] if len(pieces) == 1 else torch.cat(pieces)
-
-        own_off, own_total = {}, 0
-        for i in range(nf):
-            if not is_device_tensor(out_raw[i]):
-                own_off[i] = own_total
-                own_total += _up(sizes[i])
-        own = torch.empty(own_total, dtype=torch.uint8, device=device)
-        final = [own[own_off[i]:own_off[i] + sizes[i]] if i in own_off else out_raw[i][:sizes[i]] for i in range(nf)]
+    live = range(nf)  # an empty buffer's frame is refused above: every frame is decoded
+    results = [None] * nf
+    with _frames.launching(device) as (device, st):
+        src_all, offsets = _frames.stage_packed(srcs, lengths, on_dev, device)
+        own, own_off, final = _frames.place(live, sizes, out_raw, device)
         table = np.zeros(nf, dtype=_DEC_RECORD)
-        for i in range(nf):
+        for i in live:
             table[i] = (offsets[i], lengths[i], final[i].data_ptr(), sizes[i], 0)
         table_d = upload(table.view(np.uint8), device)
         ws_bytes = lib.mc_lz4_decode_workspace(nf)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         err = torch.empty(2 * nf, dtype=torch.int32, device=device)
-        st = stream(src_all)
         check(lib.mc_lz4_decode_batch(src_all.data_ptr(), table_d.data_ptr(), nf, max(sizes), ws.data_ptr(), ws_bytes,
                                       err.data_ptr(), st), "mc_lz4_decode_batch")
         codes = err.cpu().numpy().reshape(-1, 2)  # waits for the stream
@@ -286,20 +220,7 @@ def decompress_many(frames, outs=None):
             errors = {i: (int(c), int(m)) for i, (c, m) in enumerate(codes) if c}
             first = min(errors)
             raise _decode_error(_device_error_text(*errors[first], sizes[first]), errors)
-        host_all = download(own) if any(not on_dev[i] or isinstance(out_raw[i], np.ndarray) for i in own_off) \
-            else None
-        results = [None] * nf
-        for i in range(nf):
-            n = sizes[i]
-            if is_device_tensor(out_raw[i]):
-                results[i] = outs[i]
-            elif out_raw[i] is not None:  # a host destination
-                out_raw[i][:n] = host_all[own_off[i]:own_off[i] + n]
-                results[i] = outs[i]
-            elif on_dev[i]:
-                results[i] = final[i]
-            else:
-                results[i] = host_all[own_off[i]:own_off[i] + n]
+        _frames.hand_back(results, own, own_off, final, live, sizes, outs, out_raw, on_dev)
     return results
 
 
