@@ -672,6 +672,43 @@ int mc_lz4_decode_batch(const void *frames, const void *chunk_table, size_t nchu
                         size_t max_usize, void *workspace, size_t workspace_bytes,
                         int32_t *err, mc_stream_t stream);
 
+/* ---- zlib / gzip decode: DEFLATE in either container (zlib.py, gzip.py) --- */
+/* Inflate a batch of zlib (RFC 1950) or gzip (RFC 1952, one member) frames.
+ * The rules and the error codes are csrc/mc_inflate.h's (zlib's acceptance
+ * rules; for gzip as Python's GzipFile applies them).
+ *   frames       device: the frames' bytes, concatenated
+ *   frame_table  device, 8-B aligned: nframes records of 32 bytes: u64
+ *                src_off, u64 src_len (the frame inside `frames`, < 2^30),
+ *                u64 dst (device address of the output), u32 capacity (bytes
+ *                dst holds, < 2^30; dst may be 0 when it is 0), u32 container
+ *                (0 zlib, 1 gzip)
+ *   workspace    device, 8-B aligned, mc_inflate_workspace(nframes) bytes
+ *   err          device: 2 * nframes int32, zeroed here; frame i leaves
+ *                err[2i] = 0 or a positive code and err[2i+1] = the bytes
+ *                produced, or the computed checksum for a data-check error
+ * mc_inflate_size_batch: a plan launch (one thread per frame: the container
+ * header) and the sizing launch (one wave per frame: the whole DEFLATE chain
+ * with no stores); sizes[i] = the bytes frame i decodes to.  dst and capacity
+ * are not used and the trailer is not looked at.
+ * mc_inflate_decode_batch: the plan launch, the decode launch (one wave per
+ * frame through an LDS history ring sized by max_capacity, the largest
+ * capacity of the batch) and the check launch (one workgroup per frame: the
+ * Adler-32 / CRC-32 of what was produced against the trailer, gzip's ISIZE,
+ * and what follows a gzip trailer); produced[i] = the bytes written to dst.
+ * A frame that would produce more than its capacity is refused and nothing
+ * outside [dst, dst + capacity) is written; nothing outside a frame is read.
+ * One frame is one serial chain: throughput comes from the batch.
+ * Return a launch status; the records are valid once the stream has run.
+ * Present from this release on; mc_abi_version() is unchanged, callers find
+ * the three by symbol. */
+size_t mc_inflate_workspace(size_t nframes);
+int mc_inflate_size_batch(const void *frames, const void *frame_table, size_t nframes,
+                          void *workspace, size_t workspace_bytes, uint32_t *sizes,
+                          int32_t *err, mc_stream_t stream);
+int mc_inflate_decode_batch(const void *frames, const void *frame_table, size_t nframes,
+                            size_t max_capacity, void *workspace, size_t workspace_bytes,
+                            uint32_t *produced, int32_t *err, mc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

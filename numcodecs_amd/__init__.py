@@ -60,6 +60,8 @@ from . import batch  # noqa: E402,F401
 from . import blosc  # noqa: E402,F401  (Blosc decode: LZ4 / stored frames; blosc.register() registers it)
 from . import blosc_shuffle  # noqa: E402,F401  (Blosc's per-block shuffle filters)
 from . import lz4  # noqa: E402,F401  (the lz4 codec, both directions; lz4.register() registers it)
+from . import zlib  # noqa: E402,F401  (zlib frames, decode; zlib.register() registers it)
+from . import gzip  # noqa: E402,F401  (gzip frames, decode; gzip.register() registers it)
 from . import chunks  # noqa: E402,F401  (Zarr-style batched / host-streamed chunk pipelines)
 from . import graphs  # noqa: E402,F401  (HIP-graph captured chunk pipelines)
 
@@ -85,7 +87,9 @@ __all__ = [
     "blosc_shuffle",
     "chunks",
     "graphs",
+    "gzip",
     "lz4",
+    "zlib",
     "codec_registry",
     "get_codec",
     "register_codec",
