@@ -39,6 +39,8 @@
  *   mc_blosc_encode_batch .......... blosc.pyx:211-272 compress (lz4)
  *   mc_lz4_encode_batch ............ lz4.pyx:44-114 compress
  *   mc_lz4_decode_batch ............ lz4.pyx:117-193 decompress
+ *   mc_inflate_decode_batch ........ zlib.py / gzip.py decode
+ *   mc_deflate_encode_batch ........ zlib.py / gzip.py encode
  *   *_batch ........................ no reference counterpart: the Zarr caller loops
  *                                    Codec.encode per chunk; these run B equal-size
  *                                    chunks in one launch (chunk b at base + b*stride).
@@ -708,6 +710,47 @@ int mc_inflate_size_batch(const void *frames, const void *frame_table, size_t nf
 int mc_inflate_decode_batch(const void *frames, const void *frame_table, size_t nframes,
                             size_t max_capacity, void *workspace, size_t workspace_bytes,
                             uint32_t *produced, int32_t *err, mc_stream_t stream);
+
+/* ---- zlib / gzip encode: DEFLATE with dynamic Huffman codes per 64 KiB ---- */
+/* Encode a batch of chunks as zlib (RFC 1950) or gzip (RFC 1952) frames.  The
+ * format -- independent 64 KiB segments, one DEFLATE block each (stored, fixed
+ * or dynamic Huffman, whichever is smallest), byte-aligned and joined by empty
+ * stored blocks -- and the scalar encoder the kernels reproduce byte for byte
+ * are csrc/mc_deflate.h's.  Four launches for the whole batch: parse (one wave
+ * per segment: the match finder, the sequence list, the histograms), code (one
+ * wave per segment: code lengths, costs, block type), layout (one workgroup
+ * per chunk: offsets, the frame's size against its slot, header, checksum,
+ * trailer) and emit (one wave per segment: the bits).
+ *   src          device base the records' `src` are relative to (0: they are
+ *                absolute device addresses)
+ *   chunk_table  device, 8-B aligned: nchunks records of 40 bytes, one per
+ *                chunk with nbytes > 0, in segment order: u64 src, u64 dst
+ *                (device address of the output slot), u32 nbytes (1 ... 2^30 -
+ *                1), u32 dst_cap (the slot's bytes; container bytes + per
+ *                segment n_k + 5 * ceil(n_k / 65535) always suffice), u32
+ *                seg_base (index of the chunk's first 64 KiB segment in the
+ *                batch), u32 container (0 zlib, 1 gzip), u32 level (0: stored
+ *                blocks; otherwise the one parse), u32 seq_base (index of the
+ *                chunk's first sequence record in the batch; a chunk takes
+ *                ceil(nbytes / 4) records)
+ *   nsegments    the batch's segments: the sum of ceil(nbytes / 65536)
+ *   nsequences   the batch's sequence records: the sum of ceil(nbytes / 4)
+ *   workspace    device, 8-B aligned, mc_deflate_encode_workspace(nchunks,
+ *                nsegments, nsequences) bytes (8 bytes per sequence record:
+ *                twice the input, plus 1.7 KiB per segment)
+ *   cbytes_out   device: nchunks u32: the frame's size, 0 when it was refused
+ *   err          device: 2 * nchunks int32, zeroed here; chunk i leaves
+ *                err[2i] = 0, 1 (the frame does not fit dst_cap; err[2i+1] =
+ *                its size; nothing of it is written) or 2 (the record is out
+ *                of range)
+ * Returns a launch status; the records are valid once the stream has run.
+ * Present from this release on; mc_abi_version() is unchanged, callers find
+ * the two by symbol. */
+size_t mc_deflate_encode_workspace(size_t nchunks, size_t nsegments, size_t nsequences);
+int mc_deflate_encode_batch(const void *src, const void *chunk_table, size_t nchunks,
+                            size_t nsegments, size_t nsequences, void *workspace,
+                            size_t workspace_bytes, uint32_t *cbytes_out, int32_t *err,
+                            mc_stream_t stream);
 
 #ifdef __cplusplus
 }

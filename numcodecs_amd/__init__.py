@@ -62,6 +62,7 @@ from . import blosc_shuffle  # noqa: E402,F401  (Blosc's per-block shuffle filte
 from . import lz4  # noqa: E402,F401  (the lz4 codec, both directions; lz4.register() registers it)
 from . import zlib  # noqa: E402,F401  (zlib frames, decode; zlib.register() registers it)
 from . import gzip  # noqa: E402,F401  (gzip frames, decode; gzip.register() registers it)
+from . import deflate  # noqa: E402,F401  (zlib / gzip frames, encode; deflate.register() registers both directions)
 from . import chunks  # noqa: E402,F401  (Zarr-style batched / host-streamed chunk pipelines)
 from . import graphs  # noqa: E402,F401  (HIP-graph captured chunk pipelines)
 
@@ -86,6 +87,7 @@ __all__ = [
     "blosc",
     "blosc_shuffle",
     "chunks",
+    "deflate",
     "graphs",
     "gzip",
     "lz4",

@@ -191,6 +191,8 @@ _SIGNATURES = {
     "mc_inflate_workspace": [_c_size],
     "mc_inflate_size_batch": [_c_vp, _c_vp, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
     "mc_inflate_decode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
+    "mc_deflate_encode_workspace": [_c_size, _c_size, _c_size],
+    "mc_deflate_encode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
 }
 _RESTYPES = {
     "mc_host_device_pointer": ctypes.c_void_p,
@@ -210,6 +212,7 @@ _RESTYPES = {
     "mc_lz4_encode_workspace": ctypes.c_size_t,
     "mc_lz4_decode_workspace": ctypes.c_size_t,
     "mc_inflate_workspace": ctypes.c_size_t,
+    "mc_deflate_encode_workspace": ctypes.c_size_t,
 }
 
 EXPORTED = tuple(_SIGNATURES)
