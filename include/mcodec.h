@@ -41,6 +41,7 @@
  *   mc_lz4_decode_batch ............ lz4.pyx:117-193 decompress
  *   mc_inflate_decode_batch ........ zlib.py / gzip.py decode
  *   mc_deflate_encode_batch ........ zlib.py / gzip.py encode
+ *   mc_zstd_decode_batch ........... zstd.pyx:183-277 decompress
  *   *_batch ........................ no reference counterpart: the Zarr caller loops
  *                                    Codec.encode per chunk; these run B equal-size
  *                                    chunks in one launch (chunk b at base + b*stride).
@@ -710,6 +711,45 @@ int mc_inflate_size_batch(const void *frames, const void *frame_table, size_t nf
 int mc_inflate_decode_batch(const void *frames, const void *frame_table, size_t nframes,
                             size_t max_capacity, void *workspace, size_t workspace_bytes,
                             uint32_t *produced, int32_t *err, mc_stream_t stream);
+
+/* ---- zstd decode: Zstandard frames (zstd.pyx) ----------------------------- */
+/* Decode a batch of Zstandard frames (RFC 8878; one frame each, no
+ * dictionary).  The rules and the error codes are csrc/mc_zstd.h's (libzstd's
+ * acceptance where the RFC leaves a choice).
+ *   frames       device: the frames' bytes, concatenated
+ *   frame_table  device, 8-B aligned: nframes records of 32 bytes, the inflate
+ *                record: u64 src_off, u64 src_len (< 2^30), u64 dst (device
+ *                address of the output), u32 capacity (bytes dst holds, < 2^30;
+ *                dst may be 0 when it is 0), u32 reserved (0)
+ *   workspace    device, 8-B aligned, mc_zstd_workspace(nframes) bytes (128 KiB
+ *                per frame for the literals of a block, plus the stream records)
+ *   err          device: 2 * nframes int32, zeroed here; frame i leaves
+ *                err[2i] = 0 or a positive code and err[2i+1] = the bytes
+ *                produced, or the computed checksum for a checksum error
+ * mc_zstd_size_batch: a plan launch (one thread per frame: the frame header
+ * and the walk over the block headers) and the sizing launch (one wave per
+ * frame: headers, literal sizes and the sequences' lengths, no Huffman decode
+ * and no stores); sizes[i] = the bytes frame i decodes to.  dst and capacity
+ * are not used, the declared size and the checksum are not looked at.
+ * mc_zstd_decode_batch: the plan launch, the decode launch (one wave per frame
+ * through an LDS history ring sized by max_capacity, the largest capacity of
+ * the batch; matches further back read the output itself) and the check launch
+ * (one wave per frame: the bytes produced against a declared
+ * Frame_Content_Size, XXH64 against the content checksum); produced[i] = the
+ * bytes written to dst.  A frame that would produce more than its capacity is
+ * refused and nothing outside [dst, dst + capacity) is written; nothing
+ * outside a frame is read.  One frame is one serial chain: throughput comes
+ * from the batch.
+ * Return a launch status; the records are valid once the stream has run.
+ * Present from this release on; mc_abi_version() is unchanged, callers find
+ * the three by symbol. */
+size_t mc_zstd_workspace(size_t nframes);
+int mc_zstd_size_batch(const void *frames, const void *frame_table, size_t nframes,
+                       void *workspace, size_t workspace_bytes, uint32_t *sizes,
+                       int32_t *err, mc_stream_t stream);
+int mc_zstd_decode_batch(const void *frames, const void *frame_table, size_t nframes,
+                         size_t max_capacity, void *workspace, size_t workspace_bytes,
+                         uint32_t *produced, int32_t *err, mc_stream_t stream);
 
 /* ---- zlib / gzip encode: DEFLATE with dynamic Huffman codes per 64 KiB ---- */
 /* Encode a batch of chunks as zlib (RFC 1950) or gzip (RFC 1952) frames.  The

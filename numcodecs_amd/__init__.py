@@ -63,6 +63,7 @@ from . import lz4  # noqa: E402,F401  (the lz4 codec, both directions; lz4.regis
 from . import zlib  # noqa: E402,F401  (zlib frames, decode; zlib.register() registers it)
 from . import gzip  # noqa: E402,F401  (gzip frames, decode; gzip.register() registers it)
 from . import deflate  # noqa: E402,F401  (zlib / gzip frames, encode; deflate.register() registers both directions)
+from . import zstd  # noqa: E402,F401  (Zstandard frames, decode; zstd.register() registers it)
 from . import chunks  # noqa: E402,F401  (Zarr-style batched / host-streamed chunk pipelines)
 from . import graphs  # noqa: E402,F401  (HIP-graph captured chunk pipelines)
 
@@ -92,6 +93,7 @@ __all__ = [
     "gzip",
     "lz4",
     "zlib",
+    "zstd",
     "codec_registry",
     "get_codec",
     "register_codec",
