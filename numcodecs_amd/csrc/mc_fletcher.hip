@@ -739,6 +739,7 @@ int mc_shuffle_fletcher32_encode_batch(const void *src, size_t src_stride, void 
   m.src_stride = src_stride;
   m.dst_stride = dst_stride;
   m.group = 1;
+  m.vrows = 1;
   const size_t ntiles = m.tiles_per_chunk * nchunks;
   uint32_t *partials = static_cast<uint32_t *>(workspace);
   switch (es) {
@@ -783,6 +784,7 @@ int mc_fletcher32_unshuffle_batch(const void *src, size_t src_stride, void *dst,
   m.src_stride = src_stride;
   m.dst_stride = dst_stride;
   m.group = 1;
+  m.vrows = 1;
   const size_t ntiles = m.tiles_per_chunk * nchunks;
   uint32_t *partials = static_cast<uint32_t *>(workspace);
   switch (es) {

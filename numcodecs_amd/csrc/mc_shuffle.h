@@ -20,13 +20,41 @@ struct ChunkMap {
   size_t src_stride;       // bytes between chunks (source)
   size_t dst_stride;       // bytes between chunks (destination)
   unsigned group;          // consecutive tiles a block takes per grid-stride step
+  unsigned vrows;          // virtual rows of the tile order (1 = tiles in address order)
 };
 
+// Tile order of one large chunk ("virtual rows"): the chunk's tiles are cut
+// into R runs of C = ceil(ntiles / R) consecutive tiles and the block steps
+// walk the runs round-robin, so that the blocks in flight together work at R
+// places of every plane stream, as they do on a batch of R rows.  Step g of
+// mc_tile_steps(ntiles, R) takes tile (g % R) * C + g / R; a step whose image
+// is >= ntiles has no tile and is skipped.  (r, k) -> r * C + k is one-to-one
+// from [0, R) x [0, C) onto [0, R * C), which contains [0, ntiles), so the
+// visited steps map one-to-one onto the tiles for every ntiles >= 1 and every
+// R >= 1 (R > ntiles gives C = 1, the identity).  R = 1 is the identity.
+// The arithmetic is 32-bit (one short division per tile, no 64-bit division
+// routine in the kernels): ntiles + R must be below 2^32, which
+// mc_shuffle_impl checks before it sets vrows > 1.
+MC_HD size_t mc_tile_steps(size_t ntiles, unsigned vrows) {
+  if (vrows <= 1) return ntiles;
+  return (size_t)vrows * (((unsigned)ntiles + vrows - 1) / vrows);
+}
+MC_HD size_t mc_tile_of_step(size_t g, size_t ntiles, unsigned vrows) {
+  if (vrows <= 1) return g;
+  const unsigned c = ((unsigned)ntiles + vrows - 1) / vrows;
+  return (size_t)((unsigned)g % vrows) * c + (unsigned)g / vrows;
+}
+
 // Tile schedule: tiles are taken in groups of m.group consecutive tiles, groups
-// grid-strided over the blocks (group = 1 is a plain grid-stride loop).
-#define MC_FOR_TILES(tile, ntiles, m)                                               \
-  for (size_t _g = blockIdx.x; _g * (m).group < (ntiles); _g += gridDim.x)          \
-    for (size_t tile = _g * (m).group, _e = min((ntiles), tile + (m).group); tile < _e; ++tile)
+// grid-strided over the blocks (group = 1 is a plain grid-stride loop).  With
+// m.vrows > 1 (only with group = 1 and one chunk, mc_shuffle_impl) the steps
+// take their tile from mc_tile_of_step.
+#define MC_FOR_TILES(tile, ntiles, m)                                                          \
+  for (size_t _g = blockIdx.x, _n = mc_tile_steps((ntiles), (m).vrows); _g * (m).group < _n;   \
+       _g += gridDim.x)                                                                        \
+    for (size_t tile = mc_tile_of_step(_g, (ntiles), (m).vrows) * (m).group,                   \
+                _e = min((ntiles), tile + (m).group);                                          \
+         tile < _e; ++tile)
 
 // load / store the es dwords of one quad (16-B accesses where possible);
 // NT selects nontemporal global accesses, LDS accesses use NT = false.

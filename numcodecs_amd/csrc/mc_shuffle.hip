@@ -31,10 +31,18 @@ namespace {
 // ---------------------------------------------------------------------------
 // encode tile kernel
 // ---------------------------------------------------------------------------
-template <int ES, bool BITROUND, bool IN_LDS, bool OUT_LDS, bool NT, int QMUL = 1>
-__global__ __launch_bounds__(MC_BLOCK) void k_shuffle_enc(
-    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m,
-    size_t ntiles, McBitRound br) {
+// The bodies of the five large-chunk kernels (k_shuffle_enc,
+// k_bitround_shuffle4_planes, k_shuffle4_dec_pair, k_shuffle8_enc_pair,
+// k_shuffle8_dec_pair) are MC_DEV templates with the access policy split into
+// a load side and a store side (NT_LD, NT_ST: nontemporal or default-policy).
+// The policy has to be a compile-time parameter: a wave-uniform runtime branch
+// between a nontemporal and a plain store of the same value is merged by the
+// compiler into one plain store.  The __global__ templates pass <NT, NT>; the
+// mixed policies have wrapper kernels of their own (k_*_mix, below), selected
+// by V_LD_PLAIN / V_ST_PLAIN.
+template <int ES, bool BITROUND, bool IN_LDS, bool OUT_LDS, bool NT_LD, bool NT_ST, int QMUL>
+MC_DEV void shuffle_enc_body(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const ChunkMap &m,
+                             size_t ntiles, const McBitRound &br) {
   using G = Geom<ES, QMUL>;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x;
@@ -50,7 +58,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle_enc(
       mc_u32x4 v[G::NV];
 #pragma unroll
       for (int r = 0; r < G::NV; ++r)
-        v[r] = mc_ld16<NT>(s + (size_t)(r * MC_BLOCK + tid) * 16);
+        v[r] = mc_ld16<NT_LD>(s + (size_t)(r * MC_BLOCK + tid) * 16);
 #pragma unroll
       for (int r = 0; r < G::NV; ++r)
         reinterpret_cast<mc_u32x4 *>(lds)[r * MC_BLOCK + tid] = v[r];
@@ -67,7 +75,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle_enc(
       uint32_t w[G::Q][ES];
 #pragma unroll
       for (int q = 0; q < G::Q; ++q)
-        load_quad<ES, NT>(s + (size_t)(q * MC_BLOCK + tid) * 4 * ES, w[q]);
+        load_quad<ES, NT_LD>(s + (size_t)(q * MC_BLOCK + tid) * 4 * ES, w[q]);
 #pragma unroll
       for (int q = 0; q < G::Q; ++q) {
         if constexpr (BITROUND) mc_bitround_quad<ES>(w[q], br);
@@ -89,7 +97,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle_enc(
         const int b = u / G::PU;
         const int j = u - b * G::PU;
         const mc_u32x4 v = reinterpret_cast<const mc_u32x4 *>(lds)[u];
-        mc_st16<NT>(d + (size_t)b * m.count + (size_t)j * 16, v);
+        mc_st16<NT_ST>(d + (size_t)b * m.count + (size_t)j * 16, v);
       }
       __syncthreads();
     } else {
@@ -97,9 +105,23 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle_enc(
       for (int b = 0; b < ES; ++b)
 #pragma unroll
         for (int q = 0; q < G::Q; ++q)
-          mc_st4<NT>(d + (size_t)b * m.count + (size_t)(q * MC_BLOCK + tid) * 4, p[q][b]);
+          mc_st4<NT_ST>(d + (size_t)b * m.count + (size_t)(q * MC_BLOCK + tid) * 4, p[q][b]);
     }
   }
+}
+
+template <int ES, bool BITROUND, bool IN_LDS, bool OUT_LDS, bool NT, int QMUL = 1>
+__global__ __launch_bounds__(MC_BLOCK) void k_shuffle_enc(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m,
+    size_t ntiles, McBitRound br) {
+  shuffle_enc_body<ES, BITROUND, IN_LDS, OUT_LDS, NT, NT, QMUL>(src, dst, m, ntiles, br);
+}
+
+template <int ES, bool NT_LD, bool NT_ST, int QMUL>
+__global__ __launch_bounds__(MC_BLOCK) void k_shuffle_enc_mix(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m,
+    size_t ntiles, McBitRound br) {
+  shuffle_enc_body<ES, false, false, false, NT_LD, NT_ST, QMUL>(src, dst, m, ntiles, br);
 }
 
 // ---------------------------------------------------------------------------
@@ -130,10 +152,10 @@ MC_DEV void mc_bitround_quad_planes4(const uint32_t (&w)[4], uint32_t (&p)[4], c
   p[3] = mc_perm(a3, a1, 0x07060302u);
 }
 
-template <int Z, bool NT, int QMUL>
-__global__ __launch_bounds__(MC_BLOCK) void k_bitround_shuffle4_planes(
-    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles, McBitRound br,
-    uint32_t pmask) {
+template <int Z, bool NT_LD, bool NT_ST, int QMUL>
+MC_DEV void bitround_shuffle4_planes_body(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+                                          const ChunkMap &m, size_t ntiles, const McBitRound &br,
+                                          uint32_t pmask) {
   using G = Geom<4, QMUL>;
   const int tid = threadIdx.x;
   MC_FOR_TILES(tile, ntiles, m) {
@@ -143,15 +165,29 @@ __global__ __launch_bounds__(MC_BLOCK) void k_bitround_shuffle4_planes(
     uint8_t *d = dst + c * m.dst_stride + t * (size_t)G::TE;
     uint32_t w[G::Q][4], p[G::Q][4];
 #pragma unroll
-    for (int q = 0; q < G::Q; ++q) load_quad<4, NT>(s + (size_t)(q * MC_BLOCK + tid) * 16, w[q]);
+    for (int q = 0; q < G::Q; ++q) load_quad<4, NT_LD>(s + (size_t)(q * MC_BLOCK + tid) * 16, w[q]);
 #pragma unroll
     for (int q = 0; q < G::Q; ++q) mc_bitround_quad_planes4<Z>(w[q], p[q], br, pmask);
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int q = 0; q < G::Q; ++q)
-        mc_st4<NT>(d + (size_t)b * m.count + (size_t)(q * MC_BLOCK + tid) * 4, p[q][b]);
+        mc_st4<NT_ST>(d + (size_t)b * m.count + (size_t)(q * MC_BLOCK + tid) * 4, p[q][b]);
   }
+}
+
+template <int Z, bool NT, int QMUL>
+__global__ __launch_bounds__(MC_BLOCK) void k_bitround_shuffle4_planes(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles, McBitRound br,
+    uint32_t pmask) {
+  bitround_shuffle4_planes_body<Z, NT, NT, QMUL>(src, dst, m, ntiles, br, pmask);
+}
+
+template <int Z, bool NT_LD, bool NT_ST, int QMUL>
+__global__ __launch_bounds__(MC_BLOCK) void k_bitround_shuffle4_planes_mix(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles, McBitRound br,
+    uint32_t pmask) {
+  bitround_shuffle4_planes_body<Z, NT_LD, NT_ST, QMUL>(src, dst, m, ntiles, br, pmask);
 }
 
 // ---------------------------------------------------------------------------
@@ -238,10 +274,9 @@ MC_DEV uint32_t mc_pair_swap(uint32_t v) {  // value of the partner lane (lane ^
   return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
 }
 
-template <bool BITROUND, bool NT, int NV>
-__global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_enc_pair(
-    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles,
-    McBitRound br) {
+template <bool BITROUND, bool NT_LD, bool NT_ST, int NV>
+MC_DEV void shuffle8_enc_pair_body(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+                                   const ChunkMap &m, size_t ntiles, const McBitRound &br) {
   constexpr int TB = NV * 16 * MC_BLOCK, TE = TB / 8;
   const int tid = threadIdx.x;
   const bool odd = tid & 1;
@@ -252,7 +287,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_enc_pair(
     uint8_t *d = dst + c * m.dst_stride + t * (size_t)TE;
     mc_u32x4 v[NV];
 #pragma unroll
-    for (int r = 0; r < NV; ++r) v[r] = mc_ld16<NT>(s + ((size_t)r * MC_BLOCK + tid) * 16);
+    for (int r = 0; r < NV; ++r) v[r] = mc_ld16<NT_LD>(s + ((size_t)r * MC_BLOCK + tid) * 16);
 #pragma unroll
     for (int r = 0; r < NV; ++r) {
       mc_u32x4 x = v[r];
@@ -268,12 +303,26 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_enc_pair(
       else mc_tr4(x.x, x.z, a, b, p0, p1, p2, p3);       // low dwords of e0..e3
       const size_t e = (size_t)r * (16 * MC_BLOCK / 8) + 4 * (size_t)(tid >> 1);
       uint8_t *pd = d + (odd ? 4 * m.count : 0) + e;
-      mc_st4<NT>(pd, p0);
-      mc_st4<NT>(pd + m.count, p1);
-      mc_st4<NT>(pd + 2 * m.count, p2);
-      mc_st4<NT>(pd + 3 * m.count, p3);
+      mc_st4<NT_ST>(pd, p0);
+      mc_st4<NT_ST>(pd + m.count, p1);
+      mc_st4<NT_ST>(pd + 2 * m.count, p2);
+      mc_st4<NT_ST>(pd + 3 * m.count, p3);
     }
   }
+}
+
+template <bool BITROUND, bool NT, int NV>
+__global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_enc_pair(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles,
+    McBitRound br) {
+  shuffle8_enc_pair_body<BITROUND, NT, NT, NV>(src, dst, m, ntiles, br);
+}
+
+template <bool NT_LD, bool NT_ST, int NV>
+__global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_enc_pair_mix(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles,
+    McBitRound br) {
+  shuffle8_enc_pair_body<false, NT_LD, NT_ST, NV>(src, dst, m, ntiles, br);
 }
 
 // es = 8, lane pairs + an LDS-staged plane side (round 5, layout V_PAIR_LDS):
@@ -337,9 +386,9 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_enc_pair_lds(
   }
 }
 
-template <bool NT, int NV>
-__global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_dec_pair(
-    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles) {
+template <bool NT_LD, bool NT_ST, int NV>
+MC_DEV void shuffle8_dec_pair_body(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+                                   const ChunkMap &m, size_t ntiles) {
   constexpr int TB = NV * 16 * MC_BLOCK, TE = TB / 8;
   const int tid = threadIdx.x;
   const bool odd = tid & 1;
@@ -354,7 +403,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_dec_pair(
       const size_t e = (size_t)r * (16 * MC_BLOCK / 8) + 4 * (size_t)(tid >> 1);
       const uint8_t *ps = s + (odd ? 4 * m.count : 0) + e;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) pl[r][k] = mc_ld4<NT>(ps + k * m.count);
+      for (int k = 0; k < 4; ++k) pl[r][k] = mc_ld4<NT_LD>(ps + k * m.count);
     }
 #pragma unroll
     for (int r = 0; r < NV; ++r) {
@@ -363,9 +412,21 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_dec_pair(
       const uint32_t a = mc_pair_swap(odd ? w0 : w2);
       const uint32_t b = mc_pair_swap(odd ? w1 : w3);
       const mc_u32x4 o = odd ? mc_u32x4{a, w2, b, w3} : mc_u32x4{w0, a, w1, b};
-      mc_st16<NT>(d + ((size_t)r * MC_BLOCK + tid) * 16, o);
+      mc_st16<NT_ST>(d + ((size_t)r * MC_BLOCK + tid) * 16, o);
     }
   }
+}
+
+template <bool NT, int NV>
+__global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_dec_pair(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles) {
+  shuffle8_dec_pair_body<NT, NT, NV>(src, dst, m, ntiles);
+}
+
+template <bool NT_LD, bool NT_ST, int NV>
+__global__ __launch_bounds__(MC_BLOCK) void k_shuffle8_dec_pair_mix(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles) {
+  shuffle8_dec_pair_body<NT_LD, NT_ST, NV>(src, dst, m, ntiles);
 }
 
 // ---------------------------------------------------------------------------
@@ -558,9 +619,9 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle4_enc_wide(
   }
 }
 
-template <bool NT, int QMUL>
-__global__ __launch_bounds__(MC_BLOCK) void k_shuffle4_dec_pair(
-    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles) {
+template <bool NT_LD, bool NT_ST, int QMUL>
+MC_DEV void shuffle4_dec_pair_body(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+                                   const ChunkMap &m, size_t ntiles) {
   using G = Geom<4, QMUL>;
   const int tid = threadIdx.x;
   const bool odd = tid & 1;
@@ -573,8 +634,8 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle4_dec_pair(
 #pragma unroll
     for (int q = 0; q < G::Q; ++q) {
       const uint8_t *ps = s + (size_t)(q * MC_BLOCK + (tid & ~1)) * 4;
-      a[q] = mc_ld8<NT>(ps);
-      b[q] = mc_ld8<NT>(ps + m.count);
+      a[q] = mc_ld8<NT_LD>(ps);
+      b[q] = mc_ld8<NT_LD>(ps + m.count);
     }
 #pragma unroll
     for (int q = 0; q < G::Q; ++q) {
@@ -586,9 +647,21 @@ __global__ __launch_bounds__(MC_BLOCK) void k_shuffle4_dec_pair(
       if (odd) { p[0] = r0; p[1] = r1; p[2] = a[q].y; p[3] = b[q].y; }
       else { p[0] = a[q].x; p[1] = b[q].x; p[2] = r0; p[3] = r1; }
       mc_planes_to_quad<4>(p, w);
-      store_quad<4, NT>(d + (size_t)(q * MC_BLOCK + tid) * 16, w);
+      store_quad<4, NT_ST>(d + (size_t)(q * MC_BLOCK + tid) * 16, w);
     }
   }
+}
+
+template <bool NT, int QMUL>
+__global__ __launch_bounds__(MC_BLOCK) void k_shuffle4_dec_pair(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles) {
+  shuffle4_dec_pair_body<NT, NT, QMUL>(src, dst, m, ntiles);
+}
+
+template <bool NT_LD, bool NT_ST, int QMUL>
+__global__ __launch_bounds__(MC_BLOCK) void k_shuffle4_dec_pair_mix(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ChunkMap m, size_t ntiles) {
+  shuffle4_dec_pair_body<NT_LD, NT_ST, QMUL>(src, dst, m, ntiles);
 }
 
 // ---------------------------------------------------------------------------
@@ -755,6 +828,18 @@ static constexpr int V_PIPE = 256;
 // variant | V_BIG8 selects 8x larger tiles (register and lane-pair layouts)
 static constexpr int V_BIG8 = 512;
 static constexpr int V_TILE_MASK = V_BIG | V_BIG4 | V_BIG8;
+// variant | V_ST_PLAIN: default-policy stores, loads as V_NO_NT says;
+// variant | V_LD_PLAIN: default-policy loads, stores as V_NO_NT says.  Only the
+// five large-chunk kernels have the mixed policies (mix_supported); elsewhere
+// the bits are dropped.  Both together, or either with V_NO_NT, is V_NO_NT.
+static constexpr int V_ST_PLAIN = 1024;
+static constexpr int V_LD_PLAIN = 2048;
+static constexpr int V_POLICY_MASK = V_ST_PLAIN | V_LD_PLAIN;
+// bits 12-14: tile order of one chunk (mc_tile_of_step): 0 = address order,
+// k = 1..6 = 2^(k+2) virtual rows (8..256); 7 is invalid.  Ignored for a batch
+// (nchunks > 1), with a tile group > 1 and by the pipelined kernels.
+static constexpr int V_VROWS_SHIFT = 12;
+static constexpr int V_VROWS_MASK = 7 << V_VROWS_SHIFT;
 
 // Measured defaults (tools/probe_enc.py, tools/probe_shuffle_tiles.py on
 // MI355X, interleaved rounds; the sweeps are summarised in DESIGN.md).  Large
@@ -773,10 +858,33 @@ static int tile_flag(size_t count, size_t base_elems, int want) {
   return 0;
 }
 
-static int default_variant(size_t es, bool enc, size_t total_bytes, size_t count, size_t nchunks,
+// The Shuffle(4) encode of ONE chunk of 128-256 MiB (it fits the 256 MiB
+// Infinity Cache) stores with the default policy (V_ST_PLAIN; loads stay
+// nontemporal): whatever reads the encoded bytes next on the GPU then finds
+// part of them on-die.  Measured as the encode -> decode pair against the
+// all-nontemporal kernels (tools/probe_shuffle_pair.py,
+// profiles/r07/probe_shuffle_pair.json; G = the pair's gain, S = the parent's
+// spread over the rounds, L = what the encode alone loses on cold buffers;
+// adopted where G > 3 S and L <= G / 3):
+//   es 4  128 MiB G 6.1 (S 1.1, L 1.5)   256 MiB G 14.9 (S 2.2, L 4.1) us
+// Not adopted: es 4 at 64 MiB (G 2.7 < 3 S = 14); 512 MiB (the pair loses
+// 3.4 us: a chunk beyond the cache keeps nt); es 8 (G 5.4 / 16.2 / 21.4 us at
+// 64 / 128 / 256 MiB with L -1.2 / 1.6 / 4.4 in the probe, but the benchmark's
+// cfg_C2_f64, which times the encode alone, went 91.3 -> 99.1 us: L = 7.8 >
+// G / 3 = 7.1 on the yardstick's own layout); default-policy loads on either
+// kernel (the pair loses 2-9 us); BitRound + Shuffle(4) (L 6.4 us at 256 MiB,
+// no pair measured); a batch of chunks (unchanged).
+static bool plain_stores(size_t es, size_t chunk_bytes, size_t nchunks, bool br) {
+  return es == 4 && nchunks == 1 && !br && chunk_bytes >= ((size_t)128 << 20) &&
+         chunk_bytes <= ((size_t)256 << 20);
+}
+
+static int default_variant(size_t es, bool enc, size_t chunk_bytes, size_t count, size_t nchunks, bool br,
                            unsigned *grid_cap) {
+  const size_t total_bytes = chunk_bytes * nchunks;
   *grid_cap = 0x7fffffffu;
   if (total_bytes < ((size_t)64 << 20)) return V_REG;
+  const int st = enc && plain_stores(es, chunk_bytes, nchunks, br) ? V_ST_PLAIN : 0;
   switch (es) {
     case 2: return V_REG | tile_flag(count, 4096, V_BIG4);  // 6.34 / 6.22 TB/s
     // encode of one chunk: 32768-element tiles (128 KiB per workgroup, 32
@@ -789,7 +897,7 @@ static int default_variant(size_t es, bool enc, size_t total_bytes, size_t count
     // profiles/r01/shuffle4_pair_ab.log; larger pair tiles measured slower)
     case 4:
       if (enc && nchunks > 1 && count * 4 < ((size_t)64 << 20)) return V_PAIR | tile_flag(count, 4096, V_BIG);
-      return enc ? (V_REG | tile_flag(count, 4096, V_BIG8)) : (V_PAIR | tile_flag(count, 4096, V_BIG));
+      return enc ? (V_REG | tile_flag(count, 4096, V_BIG8) | st) : (V_PAIR | tile_flag(count, 4096, V_BIG));
     case 8:  // lane pairs keep the 8-B element side lane-contiguous
       return enc ? V_PAIR : (V_PAIR | tile_flag(count, 2048, V_BIG));  // 5.89 / 6.11 TB/s
     default:
@@ -797,6 +905,53 @@ static int default_variant(size_t es, bool enc, size_t total_bytes, size_t count
       *grid_cap = MC_MAX_GRID;
       return V_BOTH_LDS;
   }
+}
+
+// the kernels that exist with a mixed access policy (k_*_mix); `layout` is
+// the normalised layout | tile bits
+static bool mix_supported(size_t es, bool enc, bool br, int layout) {
+  if (enc && es == 4 && !br) return layout == (V_REG | V_BIG8) || layout == (V_REG | V_BIG4);
+  if (enc && es == 4) return layout == (V_REG | V_BIG4) && mc_sched.br_planes;
+  if (enc && es == 8) return !br && layout == V_PAIR;
+  return (es == 4 || es == 8) && layout == (V_PAIR | V_BIG);
+}
+
+template <int ES, bool BR, bool NT_LD, bool NT_ST>
+static int launch_enc_mix(int layout, const uint8_t *s, uint8_t *d, const ChunkMap &m,
+                          size_t ntiles, unsigned grid, const McBitRound &br, hipStream_t st) {
+  if constexpr (ES == 4 && !BR) {
+    if (layout == (V_REG | V_BIG8))
+      k_shuffle_enc_mix<4, NT_LD, NT_ST, 8><<<grid, MC_BLOCK, 0, st>>>(s, d, m, ntiles, br);
+    else if (layout == (V_REG | V_BIG4))
+      k_shuffle_enc_mix<4, NT_LD, NT_ST, 4><<<grid, MC_BLOCK, 0, st>>>(s, d, m, ntiles, br);
+    else return MC_EINVAL;
+    return mc_last_launch();
+  }
+  if constexpr (ES == 4 && BR) {
+    if (layout != (V_REG | V_BIG4) || !mc_sched.br_planes) return MC_EINVAL;
+    const int z = br.maskbits / 8;
+    const uint32_t pmask = 0x01010101u * (uint32_t)((br.mask >> (8 * z)) & 0xffu);
+    if (z == 0) k_bitround_shuffle4_planes_mix<0, NT_LD, NT_ST, 4><<<grid, MC_BLOCK, 0, st>>>(s, d, m, ntiles, br, pmask);
+    else if (z == 1) k_bitround_shuffle4_planes_mix<1, NT_LD, NT_ST, 4><<<grid, MC_BLOCK, 0, st>>>(s, d, m, ntiles, br, pmask);
+    else k_bitround_shuffle4_planes_mix<2, NT_LD, NT_ST, 4><<<grid, MC_BLOCK, 0, st>>>(s, d, m, ntiles, br, pmask);
+    return mc_last_launch();
+  }
+  if constexpr (ES == 8 && !BR) {
+    if (layout != V_PAIR) return MC_EINVAL;
+    k_shuffle8_enc_pair_mix<NT_LD, NT_ST, 4><<<grid, MC_BLOCK, 0, st>>>(s, d, m, ntiles, br);
+    return mc_last_launch();
+  }
+  return MC_EINVAL;
+}
+
+template <int ES, bool NT_LD, bool NT_ST>
+static int launch_dec_mix(int layout, const uint8_t *s, uint8_t *d, const ChunkMap &m,
+                          size_t ntiles, unsigned grid, hipStream_t st) {
+  if (layout != (V_PAIR | V_BIG)) return MC_EINVAL;
+  if constexpr (ES == 4) k_shuffle4_dec_pair_mix<NT_LD, NT_ST, 2><<<grid, MC_BLOCK, 0, st>>>(s, d, m, ntiles);
+  else if constexpr (ES == 8) k_shuffle8_dec_pair_mix<NT_LD, NT_ST, 8><<<grid, MC_BLOCK, 0, st>>>(s, d, m, ntiles);
+  else return MC_EINVAL;
+  return mc_last_launch();
 }
 
 template <int ES, bool BR, bool NT>
@@ -891,6 +1046,8 @@ static int launch_enc_tiles(int variant, const uint8_t *s, uint8_t *d, const Chu
   if ((layout & 7) == V_PAIR_LDS && (ES != 8 || (layout & (V_PIPE | V_BIG8)))) return MC_EINVAL;
   if ((layout & 7) == V_WIDE && ((ES != 4 && ES != 8) || (layout & (V_PIPE | V_BIG8)))) return MC_EINVAL;
   if ((layout & V_BIG8) && (layout & V_PIPE)) return MC_EINVAL;
+  if (variant & V_ST_PLAIN) return launch_enc_mix<ES, BR, true, false>(layout, s, d, m, ntiles, grid, br, st);
+  if (variant & V_LD_PLAIN) return launch_enc_mix<ES, BR, false, true>(layout, s, d, m, ntiles, grid, br, st);
   if (variant & V_NO_NT) launch_enc_nt<ES, BR, false>(layout, s, d, m, ntiles, grid, br, st);
   else launch_enc_nt<ES, BR, true>(layout, s, d, m, ntiles, grid, br, st);
   return mc_last_launch();
@@ -952,6 +1109,8 @@ static int launch_dec_tiles(int variant, const uint8_t *s, uint8_t *d, const Chu
   if ((layout & 7) == V_PAIR && ES != 8 && ES != 4) return MC_EINVAL;
   if ((layout & 7) == V_WIDE && (ES != 8 || (layout & (V_PIPE | V_BIG8)))) return MC_EINVAL;
   if ((layout & V_BIG8) && (layout & V_PIPE)) return MC_EINVAL;
+  if (variant & V_ST_PLAIN) return launch_dec_mix<ES, true, false>(layout, s, d, m, ntiles, grid, st);
+  if (variant & V_LD_PLAIN) return launch_dec_mix<ES, false, true>(layout, s, d, m, ntiles, grid, st);
   if (variant & V_NO_NT) launch_dec_nt<ES, false>(layout, s, d, m, ntiles, grid, st);
   else launch_dec_nt<ES, true>(layout, s, d, m, ntiles, grid, st);
   return mc_last_launch();
@@ -993,10 +1152,12 @@ int mc_shuffle_impl(const void *src_, size_t src_stride, void *dst_, size_t dst_
   m.src_stride = nchunks > 1 ? src_stride : 0;
   m.dst_stride = nchunks > 1 ? dst_stride : 0;
   m.group = 1;
+  m.vrows = 1;
+  if ((variant & V_VROWS_MASK) == V_VROWS_MASK) return MC_EINVAL;
 
   unsigned default_cap = MC_MAX_GRID;
   if (variant == V_DEFAULT) {
-    variant = default_variant(es, enc, chunk_bytes * nchunks, m.count, nchunks, &default_cap);
+    variant = default_variant(es, enc, chunk_bytes, m.count, nchunks, br != nullptr, &default_cap);
     // BitRound + Shuffle(4) of a large chunk: the plane-masked kernel on 64
     // KiB tiles (half the registers of the 128 KiB tiles, twice the waves to
     // hide its BitRound VALU): 256 MiB 89.2-89.4 against 89.7-91.0 us for
@@ -1029,13 +1190,22 @@ int mc_shuffle_impl(const void *src_, size_t src_stride, void *dst_, size_t dst_
     if (variant & V_PIPE) variant &= ~(V_GROUP_MASK | V_BIG8);
     if (variant & V_BIG8) variant &= ~(V_BIG | V_BIG4);
     if (variant & V_BIG4) variant &= ~V_BIG;
+    if (variant & V_POLICY_MASK) {
+      if ((variant & V_NO_NT) || (variant & V_POLICY_MASK) == V_POLICY_MASK)
+        variant = (variant & ~V_POLICY_MASK) | V_NO_NT;
+      else if (!mix_supported(es, enc, br != nullptr, variant & (7 | V_TILE_MASK | V_PIPE)))
+        variant &= ~V_POLICY_MASK;
+    }
     m.group = 1u << ((variant & V_GROUP_MASK) >> V_GROUP_SHIFT);
     const size_t te = tile_elems(es, variant);
     m.tiles_per_chunk = m.count / te;
     const size_t ntiles = m.tiles_per_chunk * nchunks;
+    if ((variant & V_VROWS_MASK) && nchunks == 1 && m.group == 1 && !(variant & V_PIPE) &&
+        ntiles < ((size_t)1 << 31))
+      m.vrows = 1u << (((variant & V_VROWS_MASK) >> V_VROWS_SHIFT) + 2);
     if (ntiles > 0) {
       unsigned cap = max_blocks > 0 ? (unsigned)max_blocks : MC_MAX_GRID;
-      unsigned grid = mc_grid_for(ntiles, m.group, cap);
+      unsigned grid = mc_grid_for(mc_tile_steps(ntiles, m.vrows), m.group, cap);
       int rc = MC_EINVAL;
       if (enc) {
         switch (es) {

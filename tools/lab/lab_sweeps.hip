@@ -42,7 +42,9 @@ int mc_lab_c4_dec1p(const void *src, void *dst, size_t n, int astype, int dtype,
 // bits 0-2 layout (0 default, 1 register/dword stores, 2 LDS-staged 16-B
 // stores, 3 LDS both sides, 4 generic byte kernel, 5 lane pairs), | 8
 // temporal accesses, | 16 / | 128 2x / 4x tiles, bits 5-6 tile group,
-// | 256 software-pipelined persistent loop, | 512 8x tiles.  max_blocks 0 =
+// | 256 software-pipelined persistent loop, | 512 8x tiles, | 1024 / | 2048
+// default-policy stores / loads (the five large-chunk kernels), bits 12-14
+// tile order of one chunk (k = 1..6: 2^(k+2) virtual rows).  max_blocks 0 =
 // one workgroup per tile, the product's grid for large buffers (round 4:
 // until then 0 capped an explicit layout at MC_MAX_GRID = 2048 workgroups,
 // which made every layout with more than 2048 tiles loop and measure slower
@@ -53,7 +55,7 @@ static int lab_grid_cap(int max_blocks) {
 
 int mc_lab_shuffle_variant(const void *src, void *dst, size_t nbytes, size_t elementsize, int encode,
                            int variant, int max_blocks, mc_stream_t stream) {
-  if (variant < 0 || (variant & ~0x3FF) != 0) return MC_EINVAL;
+  if (variant < 0 || (variant & ~0x7FFF) != 0) return MC_EINVAL;
   max_blocks = lab_grid_cap(max_blocks);
   return mc_shuffle_impl(src, 0, dst, 0, 1, nbytes, elementsize, encode != 0, variant, max_blocks, nullptr,
                          (hipStream_t)stream);
@@ -63,7 +65,7 @@ int mc_lab_shuffle_variant(const void *src, void *dst, size_t nbytes, size_t ele
 // layout, as mc_lab_shuffle_variant
 int mc_lab_shuffle_batch_variant(const void *src, size_t ss, void *dst, size_t ds, size_t nchunks, size_t nbytes,
                                  size_t elementsize, int encode, int variant, int max_blocks, mc_stream_t stream) {
-  if (variant < 0 || (variant & ~0x3FF) != 0) return MC_EINVAL;
+  if (variant < 0 || (variant & ~0x7FFF) != 0) return MC_EINVAL;
   max_blocks = lab_grid_cap(max_blocks);
   return mc_shuffle_impl(src, ss, dst, ds, nchunks, nbytes, elementsize, encode != 0, variant, max_blocks, nullptr,
                          (hipStream_t)stream);
@@ -73,7 +75,7 @@ int mc_lab_shuffle_batch_variant(const void *src, size_t ss, void *dst, size_t d
 // explicit layout, as mc_lab_shuffle_variant.
 int mc_lab_bitround_shuffle_variant(const void *src, void *dst, size_t n, int itemsize, int keepbits,
                                     int variant, int max_blocks, mc_stream_t stream) {
-  if (variant < 0 || (variant & ~0x3FF) != 0) return MC_EINVAL;
+  if (variant < 0 || (variant & ~0x7FFF) != 0) return MC_EINVAL;
   if (!(itemsize == 2 || itemsize == 4 || itemsize == 8)) return MC_EINVAL;
   const int mbits = itemsize == 2 ? 10 : itemsize == 4 ? 23 : 52;
   if (keepbits < 0 || keepbits >= mbits) return MC_EINVAL;
