@@ -42,6 +42,7 @@
  *   mc_inflate_decode_batch ........ zlib.py / gzip.py decode
  *   mc_deflate_encode_batch ........ zlib.py / gzip.py encode
  *   mc_zstd_decode_batch ........... zstd.pyx:183-277 decompress
+ *   mc_zstd_encode_batch ........... zstd.pyx:96-180 compress
  *   *_batch ........................ no reference counterpart: the Zarr caller loops
  *                                    Codec.encode per chunk; these run B equal-size
  *                                    chunks in one launch (chunk b at base + b*stride).
@@ -791,6 +792,49 @@ int mc_deflate_encode_batch(const void *src, const void *chunk_table, size_t nch
                             size_t nsegments, size_t nsequences, void *workspace,
                             size_t workspace_bytes, uint32_t *cbytes_out, int32_t *err,
                             mc_stream_t stream);
+
+/* ---- zstd encode: Zstandard frames, Huffman literals and FSE sequences ----- */
+/* Encode a batch of chunks as Zstandard (RFC 8878) frames, one frame each, no
+ * dictionary, Frame_Content_Size declared.  The format -- independent 64 KiB
+ * segments, one block each (raw, RLE or compressed, whichever is smallest),
+ * raw or Huffman-compressed literals, LL / OF / ML in predefined, RLE or
+ * FSE-compressed mode -- and the scalar encoder the kernels reproduce byte for
+ * byte are csrc/mc_zstd_enc.h's.  Four launches for the whole batch: parse (one
+ * wave per segment: the match finder, the sequence list, the literals, the
+ * histograms), code (one wave per segment: Huffman lengths and tree
+ * description, normalisations, modes, the three state chains, every size),
+ * layout (one workgroup per chunk: offsets, the frame's size against its slot,
+ * header, XXH64) and emit (one wave per segment: the bits).
+ *   src          device base the records' `src` are relative to (0: they are
+ *                absolute device addresses)
+ *   chunk_table  device, 8-B aligned: nchunks records of 40 bytes, one per
+ *                chunk with nbytes > 0, in segment order: u64 src, u64 dst
+ *                (device address of the output slot), u32 nbytes (1 ... 2^30 -
+ *                1), u32 dst_cap (the slot's bytes; header (6 / 7 / 10 bytes
+ *                for nbytes <= 255 / <= 65536 / above) + 3 per segment + nbytes
+ *                + 4 with the checksum always suffice), u32 seg_base (index of
+ *                the chunk's first 64 KiB segment in the batch), u32 seq_base
+ *                (index of the chunk's first sequence record in the batch; a
+ *                chunk takes ceil(nbytes / 4) records), u32 flags (1: append
+ *                the content checksum), u32 reserved (0)
+ *   nsegments    the batch's segments: the sum of ceil(nbytes / 65536)
+ *   nsequences   the batch's sequence records: the sum of ceil(nbytes / 4)
+ *   workspace    device, 8-B aligned, mc_zstd_encode_workspace(nchunks,
+ *                nsegments, nsequences) bytes (20 bytes per sequence record:
+ *                five times the input, plus 2.4 KiB per segment)
+ *   cbytes_out   device: nchunks u32: the frame's size, 0 when it was refused
+ *   err          device: 2 * nchunks int32, zeroed here; chunk i leaves
+ *                err[2i] = 0, 1 (the frame does not fit dst_cap; err[2i+1] =
+ *                its size; nothing of it is written) or 2 (the record is out
+ *                of range)
+ * Returns a launch status; the records are valid once the stream has run.
+ * Present from this release on; mc_abi_version() is unchanged, callers find
+ * the two by symbol. */
+size_t mc_zstd_encode_workspace(size_t nchunks, size_t nsegments, size_t nsequences);
+int mc_zstd_encode_batch(const void *src, const void *chunk_table, size_t nchunks,
+                         size_t nsegments, size_t nsequences, void *workspace,
+                         size_t workspace_bytes, uint32_t *cbytes_out, int32_t *err,
+                         mc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,7 @@ from . import zlib  # noqa: E402,F401  (zlib frames, decode; zlib.register() reg
 from . import gzip  # noqa: E402,F401  (gzip frames, decode; gzip.register() registers it)
 from . import deflate  # noqa: E402,F401  (zlib / gzip frames, encode; deflate.register() registers both directions)
 from . import zstd  # noqa: E402,F401  (Zstandard frames, decode; zstd.register() registers it)
+from . import zstd_enc  # noqa: E402,F401  (Zstandard frames, encode; zstd_enc.register() registers both directions)
 from . import chunks  # noqa: E402,F401  (Zarr-style batched / host-streamed chunk pipelines)
 from . import graphs  # noqa: E402,F401  (HIP-graph captured chunk pipelines)
 
@@ -94,6 +95,7 @@ __all__ = [
     "lz4",
     "zlib",
     "zstd",
+    "zstd_enc",
     "codec_registry",
     "get_codec",
     "register_codec",

@@ -196,6 +196,8 @@ _SIGNATURES = {
     "mc_zstd_workspace": [_c_size],
     "mc_zstd_size_batch": [_c_vp, _c_vp, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
     "mc_zstd_decode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
+    "mc_zstd_encode_workspace": [_c_size, _c_size, _c_size],
+    "mc_zstd_encode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
 }
 _RESTYPES = {
     "mc_host_device_pointer": ctypes.c_void_p,
@@ -217,6 +219,7 @@ _RESTYPES = {
     "mc_inflate_workspace": ctypes.c_size_t,
     "mc_deflate_encode_workspace": ctypes.c_size_t,
     "mc_zstd_workspace": ctypes.c_size_t,
+    "mc_zstd_encode_workspace": ctypes.c_size_t,
 }
 
 EXPORTED = tuple(_SIGNATURES)

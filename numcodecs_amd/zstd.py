@@ -10,8 +10,10 @@ reference's ``RuntimeError`` with its text for the condition and
 ``frame_errors`` naming the batch's rejected frames; see
 :mod:`numcodecs_amd._zstd` for the launches and read-backs per batch.
 
-Encoding stays on the host: :meth:`Zstd.encode` raises ``NotImplementedError``
-(use ``numcodecs.Zstd``; its frames decode here).
+This module is decode only: :meth:`Zstd.encode` raises ``NotImplementedError``
+(use ``numcodecs.Zstd``; its frames decode here).  The write side on the GPU
+is :mod:`numcodecs_amd.zstd_enc`, whose ``Zstd`` is this class with ``encode``
+added.
 
 The codec is not registered on import: call :func:`register`.
 """
