@@ -36,7 +36,9 @@
  *   mc_blosc_filter ................ blosc.pyx:67-71,211-326 SHUFFLE / BITSHUFFLE as
  *                                    c-blosc applies them per block (shuffle.c)
  *   mc_blosc_decode_batch .......... blosc.pyx:274-326 decompress (lz4 / lz4hc / stored)
+ *   mc_blosc_decode_batch_z ........ blosc.pyx:274-326 decompress (those, zlib and zstd)
  *   mc_blosc_encode_batch .......... blosc.pyx:211-272 compress (lz4)
+ *   mc_blosc_encode_batch_z ........ blosc.pyx:211-272 compress (zstd)
  *   mc_lz4_encode_batch ............ lz4.pyx:44-114 compress
  *   mc_lz4_decode_batch ............ lz4.pyx:117-193 decompress
  *   mc_inflate_decode_batch ........ zlib.py / gzip.py decode
@@ -582,6 +584,54 @@ int mc_blosc_decode_batch(const void *frames, const void *frame_table,
                           size_t workspace_bytes, int32_t *err,
                           mc_stream_t stream);
 
+/* ---- Blosc decompression: lz4, zlib and zstd frames in one batch --------- */
+/* mc_blosc_decode_batch for a batch that may also hold frames whose
+ * compressor format is 3 (zlib: every stream one zlib frame, RFC 1950) or 4
+ * (zstd: every stream one Zstandard frame, RFC 8878): one plan launch, then
+ * one decode launch per format present (one wave per stream over the shared
+ * descriptor list; a wave whose stream is another format's leaves at once).
+ * The streams are held to the stand-alone decoders' rules (csrc/mc_zstd.h:
+ * no dictionary, nothing behind the frame, a content checksum verified;
+ * csrc/mc_inflate.h: Adler-32 verified, what follows the trailer ignored) and
+ * each must produce exactly its share of its block (csrc/mc_blosc_z.h).
+ *   frame_table  device, 8-B aligned: nframes records of 56 bytes: the 48
+ *                bytes of mc_blosc_decode_batch's record, then u64 lit_off:
+ *                for a zstd frame that is not memcpyed, the offset of the
+ *                frame's nbytes bytes in the literals area (ranges must not
+ *                overlap); unused otherwise
+ *   max_lz4, max_zlib, max_zstd  the largest stream's uncompressed size among
+ *                the frames of that format (memcpyed frames count as lz4
+ *                whatever their format bits say); 0 = no such frame, no launch
+ *   lit_bytes    the literals area: a zstd stream decodes the Huffman
+ *                literals of one block into min(share, 128 KiB) bytes at its
+ *                own offset in its frame's range, so the area is the sum of
+ *                nbytes over the zstd frames (each range a multiple of 16 is
+ *                what the Python layer asks for) -- bounded by the batch's
+ *                output, not 128 KiB per stream
+ *   workspace    device, 8-B aligned, mc_blosc_decode_batch_z_workspace(
+ *                nstreams, lit_bytes) bytes = 32 * nstreams rounded up to 16,
+ *                + lit_bytes + 16
+ *   err          as mc_blosc_decode_batch's.  The code of an lz4 frame is
+ *                csrc/mc_lz4.h's; of a zstd frame mc_zstd_error
+ *                (csrc/mc_zstd.h) for a violation inside a stream (a declared
+ *                size other than the share, or fewer bytes: MC_ZSTD_E_SIZE;
+ *                more: MC_ZSTD_E_CAPACITY); of a zlib frame mc_inf_error
+ *                (csrc/mc_inflate.h; fewer bytes: MC_INF_E_LENGTH, more:
+ *                MC_INF_E_CAPACITY); a violation of the container of a zstd
+ *                or zlib frame is 64 + the mc_lz4_error.  A frame of another
+ *                format is refused (MC_LZ4_E_TABLE) and nothing of it decoded.
+ * LDS per workgroup: lz4 the history ring (<= 64 KiB); zstd the ring (<= 64
+ * KiB) + 11.3 KiB of tables; zlib the ring (<= 32 KiB) + 3.7 KiB of tables.
+ * Present from this release on; mc_abi_version() is unchanged, callers find
+ * the pair by symbol. */
+size_t mc_blosc_decode_batch_z_workspace(size_t nstreams, size_t lit_bytes);
+int mc_blosc_decode_batch_z(const void *frames, const void *frame_table,
+                            size_t nframes, size_t nblocks, size_t nstreams,
+                            size_t max_lz4, size_t max_zlib, size_t max_zstd,
+                            size_t lit_bytes, void *workspace,
+                            size_t workspace_bytes, int32_t *err,
+                            mc_stream_t stream);
+
 /* ---- Blosc compression: LZ4 frames (blosc.pyx:211-272) ------------------- */
 /* Encode a batch of already-filtered buffers (mc_blosc_filter(forward = 1))
  * as Blosc1 LZ4 frames: one compress launch (one wave per stream, LZ4 blocks
@@ -619,6 +669,51 @@ int mc_blosc_encode_batch(const void *src, const void *frame_table,
                           size_t nframes, size_t nblocks, size_t nstreams,
                           void *workspace, size_t workspace_bytes,
                           uint32_t *cbytes_out, mc_stream_t stream);
+
+/* ---- Blosc compression: zstd frames (blosc.pyx:211-272, cname='zstd') ---- */
+/* mc_blosc_encode_batch for frames whose compressor format is 4 (zstd): the
+ * header flags carry format bits 4 and always the do-not-split bit, so a
+ * stream is a block, and every block becomes one Zstandard frame (RFC 8878:
+ * independent 64 KiB segments, Frame_Content_Size declared, no checksum) in
+ * the block's scratch slot with a capacity of the block's size - 1; a frame
+ * that would not fit (the block does not get smaller) makes the stream raw.
+ * Eight launches per batch, whatever it holds: chunks (one thread per block:
+ * the Zstandard encoder's chunk record), mc_zstd_encode_batch's parse, code,
+ * layout and emit over all blocks as its chunks, bridge (one thread per
+ * block: the encoder's size / error record -> the stream's size, 0 = raw),
+ * then mc_blosc_encode_batch's layout and gather (bstarts, cbytes words,
+ * header, the memcpyed decision above nbytes + 16).
+ *   frame_table  as mc_blosc_encode_batch's (56-byte records); flags must
+ *                carry bit 4 (0x10) and must not carry bit 1 (memcpyed:
+ *                such frames go through mc_blosc_encode_batch, which writes
+ *                whatever format bits the flags hold); stream_base ==
+ *                block_base
+ *   frame_bases  device, 4-B aligned: 2 u32 per frame: the index of the
+ *                frame's first segment and of its first sequence record in
+ *                the batch -- running sums over the frames' blocks of
+ *                ceil(block bytes / 65536) and ceil(block bytes / 4): pure
+ *                functions of nbytes and blocksize (the blocks before a
+ *                frame's last are blocksize bytes)
+ *   nblocks, nsegments, nsequences  the batch's totals (nsequences < 2^32)
+ *   workspace    device, 8-B aligned, mc_blosc_encode_batch_z_workspace(
+ *                nblocks, nsegments, nsequences, scratch_bytes) bytes: the
+ *                stream words (12 B per block), the chunk table (40 B), the
+ *                encoder's size and error records (12 B), each rounded up to
+ *                256, mc_zstd_encode_workspace(nblocks, nsegments,
+ *                nsequences) rounded up to 256, then scratch_bytes of scratch
+ *   cbytes_out   as mc_blosc_encode_batch's; a frame whose record is refused
+ *                (also: a missing do-not-split bit, a memcpyed bit) is 0.
+ * The bytes are those of the host model (tests/native_blosc_z: the scalar
+ * encoder of csrc/mc_zstd_enc.h and the layout helpers of csrc/mc_lz4_enc.h).
+ * Returns a launch status.  Present from this release on; mc_abi_version()
+ * is unchanged, callers find the pair by symbol. */
+size_t mc_blosc_encode_batch_z_workspace(size_t nblocks, size_t nsegments,
+                                         size_t nsequences, size_t scratch_bytes);
+int mc_blosc_encode_batch_z(const void *src, const void *frame_table,
+                            const uint32_t *frame_bases, size_t nframes,
+                            size_t nblocks, size_t nsegments, size_t nsequences,
+                            void *workspace, size_t workspace_bytes,
+                            uint32_t *cbytes_out, mc_stream_t stream);
 
 /* ---- LZ4 codec: a size word + one LZ4 block per chunk (lz4.pyx) ---------- */
 /* Encode a batch of chunks as `lz4` frames (u32 LE nbytes, then one LZ4

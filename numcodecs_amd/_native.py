@@ -196,6 +196,11 @@ _SIGNATURES = {
     "mc_zstd_workspace": [_c_size],
     "mc_zstd_size_batch": [_c_vp, _c_vp, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
     "mc_zstd_decode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
+    "mc_blosc_decode_batch_z_workspace": [_c_size, _c_size],
+    "mc_blosc_decode_batch_z": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_size, _c_size, _c_size, _c_size, _c_vp,
+                                _c_size, _c_vp, _c_vp],
+    "mc_blosc_encode_batch_z_workspace": [_c_size, _c_size, _c_size, _c_size],
+    "mc_blosc_encode_batch_z": [_c_vp, _c_vp, _c_vp, _c_size, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp],
     "mc_zstd_encode_workspace": [_c_size, _c_size, _c_size],
     "mc_zstd_encode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
 }
@@ -220,6 +225,8 @@ _RESTYPES = {
     "mc_deflate_encode_workspace": ctypes.c_size_t,
     "mc_zstd_workspace": ctypes.c_size_t,
     "mc_zstd_encode_workspace": ctypes.c_size_t,
+    "mc_blosc_decode_batch_z_workspace": ctypes.c_size_t,
+    "mc_blosc_encode_batch_z_workspace": ctypes.c_size_t,
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -30,11 +30,6 @@ namespace {
 
 using namespace mc_lz4w;
 
-MC_DEV void record_error(int32_t *err, uint32_t frame, int code, uint32_t stream) {
-  // first error of a frame wins; plain vector atomics / stores
-  if (atomicCAS(reinterpret_cast<int *>(&err[2 * frame]), 0, code) == 0) err[2 * frame + 1] = (int32_t)stream;
-}
-
 __global__ void __launch_bounds__(MC_BLOCK)
 plan_kernel(const uint8_t *__restrict__ frames, const mc_blosc_frame *__restrict__ table, uint32_t nframes,
             uint32_t nblocks_total, mc_lz4_stream *__restrict__ streams, uint32_t nstreams_total,
@@ -57,20 +52,7 @@ __global__ void __launch_bounds__(WAVE)
 decode_kernel(const uint8_t *__restrict__ frames, const mc_lz4_stream *__restrict__ streams, uint32_t nstreams,
               uint32_t ring_mask, int32_t *__restrict__ err) {
   extern __shared__ uint8_t ring[];
-  const uint32_t sidx = blockIdx.x, lane = threadIdx.x;
-  if (sidx >= nstreams) return;
-  const mc_lz4_stream d = streams[sidx];
-  if (!(d.flags & MC_LZ4_S_VALID)) return;
-  const uint8_t *src = frames + d.src_off;
-  uint8_t *dst = reinterpret_cast<uint8_t *>((uintptr_t)d.dst);
-  const uint32_t n = uni(d.cbytes), usize = uni(d.usize);
-  if (d.flags & MC_LZ4_S_RAW) {  // cbytes == usize (plan)
-    for (uint32_t k = lane; k < usize; k += WAVE) dst[k] = src[k];
-    return;
-  }
-  uint32_t produced;
-  const int e = decode_wave(src, n, dst, usize, ring, ring_mask, lane, &produced);
-  if (e != MC_LZ4_OK && lane == 0) record_error(err, d.frame, e, sidx);
+  blosc_lz4_stream(frames, streams, nstreams, 0u, ring, ring_mask, err);  // shared with mc_blosc_dec_z.hip
 }
 
 }  // namespace

@@ -21,9 +21,23 @@
 // gather:   one workgroup per stream copies the cbytes word and the stream's
 //           bytes (scratch, or the filtered source when raw) into the frame's
 //           slot; for a memcpyed frame its share of the unfiltered input.
+//
+// cname='zstd' (mc_blosc_encode_batch_z): the frames always carry the
+// do-not-split bit, so a stream is a block, and every block becomes one
+// Zstandard frame through mc_zstd_encode_batch's four kernels (parse / code /
+// layout / emit: 64 KiB segments, Frame_Content_Size, no checksum) in the place
+// of `compress`:
+// chunks:   one thread per block writes the encoder's chunk record: the block's
+//           filtered bytes -> its scratch slot, dst_cap = block size - 1;
+//           seg_base / seq_base from the frame's bases (pure functions of the
+//           sizes, the caller's) and the block's index.
+// bridge:   one thread per block turns the encoder's size / error record into
+//           `csize` (a refused frame -- it does not get smaller -- is 0: raw).
+// layout and gather are the ones above.
 #include "mc_common.h"
 #include "mc_lz4_enc.h"
 #include "mc_lz4_wave.h"  // encode_wave: the match finder, shared with mc_lz4_codec.hip
+#include "mc_zstd_enc.h"  // mc_zstd_enc_chunk and the segment / sequence counts (mc_blosc_encode_batch_z)
 
 namespace {
 
@@ -155,7 +169,66 @@ __global__ void __launch_bounds__(MC_BLOCK) gather_kernel(enc_args a) {
   wg_copy_bytes(from, dst + at + 4, nb);
 }
 
+// ---- cname='zstd' ----
+struct z_args {
+  enc_args e;
+  const uint32_t *bases;     // per frame: index of its first segment, of its first sequence record
+  mc_zstd_enc_chunk *chunks; // per stream
+  uint32_t *zsize;           // per stream: the encoder's cbytes_out
+  int32_t *zerr;             // per stream: the encoder's error record (2 words)
+  uint32_t nsegs;
+  uint64_t nseqs;
+};
+
+// the record of stream sidx; nbytes 0 (a chunk the encoder refuses) where the frame's record is bad
+__global__ void __launch_bounds__(MC_BLOCK) z_chunks_kernel(z_args z) {
+  const enc_args &a = z.e;
+  const uint32_t sidx = blockIdx.x * MC_BLOCK + threadIdx.x;
+  if (sidx >= a.nstreams) return;
+  const uint32_t fi = frame_of_stream(a.table, a.nframes, sidx);
+  const mc_blosc_enc_frame f = a.table[fi];
+  mc_zstd_enc_chunk c;
+  c.src = 0, c.dst = 0, c.nbytes = 0, c.dst_cap = 0, c.seg_base = 0, c.seq_base = 0, c.flags = 0, c.reserved = 0;
+  // one stream per block: the do-not-split bit is required, a memcpyed frame is the lz4 entry point's
+  if (mc_blosc_enc_frame_ok(f, a.nblocks, a.nstreams, a.scratch_bytes) && (f.flags & MC_BLOSC_F_NOSPLIT) &&
+      !(f.flags & MC_BLOSC_F_MEMCPYED) && sidx - f.stream_base < mc_blosc_nblocks(f.nbytes, f.blocksize)) {
+    uint32_t block, first, off, neb;
+    mc_blosc_enc_stream(f, sidx - f.stream_base, &block, &first, &off, &neb);
+    c.src = a.base + f.src + off;
+    c.dst = (uint64_t)(uintptr_t)(a.scratch + f.scratch_off + off);
+    c.nbytes = neb, c.dst_cap = neb - 1u;
+    // the blocks before this one are full ones (the encoder checks the bases against the batch's totals)
+    c.seg_base = z.bases[2 * fi] + block * mc_ze_nsegments(f.blocksize);
+    c.seq_base = z.bases[2 * fi + 1] + block * mc_ze_seq_records(f.blocksize);
+  }
+  z.chunks[sidx] = c;
+}
+
+__global__ void __launch_bounds__(MC_BLOCK) z_bridge_kernel(z_args z) {
+  const enc_args &a = z.e;
+  const uint32_t sidx = blockIdx.x * MC_BLOCK + threadIdx.x;
+  if (sidx >= a.nstreams) return;
+  const uint32_t n = z.chunks[sidx].nbytes, cs = z.zsize[sidx];
+  // a frame that was written is shorter than the block (dst_cap); anything else is stored raw
+  a.csize[sidx] = (z.zerr[2 * sidx] == 0 && cs > 0 && cs < n) ? cs : 0u;
+}
+
 constexpr size_t WS_ALIGN = 256;
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+struct z_layout {
+  size_t words, chunks, zsize, zerr, zws, scratch;
+};
+z_layout z_plan(size_t nstreams, size_t nsegs, size_t nseqs) {
+  z_layout w;
+  w.words = 0;
+  w.chunks = up256(3 * nstreams * sizeof(uint32_t));
+  w.zsize = w.chunks + up256(nstreams * sizeof(mc_zstd_enc_chunk));
+  w.zerr = w.zsize + up256(nstreams * sizeof(uint32_t));
+  w.zws = w.zerr + up256(2 * nstreams * sizeof(int32_t));
+  w.scratch = w.zws + up256(mc_zstd_encode_workspace(nstreams, nsegs, nseqs));
+  return w;
+}
+
 size_t words_bytes(size_t nstreams) { return (3 * nstreams * sizeof(uint32_t) + WS_ALIGN - 1) / WS_ALIGN * WS_ALIGN; }
 
 }  // namespace
@@ -188,6 +261,59 @@ int mc_blosc_encode_batch(const void *src, const void *frame_table, size_t nfram
   a.cbytes_out = cbytes_out;
   hipLaunchKernelGGL(compress_kernel, dim3((unsigned)nstreams), dim3(WAVE), 0, st, a);
   int rc = mc_last_launch();
+  if (rc != MC_OK) return rc;
+  hipLaunchKernelGGL(layout_kernel, dim3((unsigned)nframes), dim3(MC_BLOCK), 0, st, a);
+  rc = mc_last_launch();
+  if (rc != MC_OK) return rc;
+  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)nstreams), dim3(MC_BLOCK), 0, st, a);
+  return mc_last_launch();
+}
+
+size_t mc_blosc_encode_batch_z_workspace(size_t nstreams, size_t nsegments, size_t nsequences, size_t scratch_bytes) {
+  return z_plan(nstreams, nsegments, nsequences).scratch + scratch_bytes;
+}
+
+int mc_blosc_encode_batch_z(const void *src, const void *frame_table, const uint32_t *frame_bases, size_t nframes,
+                            size_t nblocks, size_t nsegments, size_t nsequences, void *workspace,
+                            size_t workspace_bytes, uint32_t *cbytes_out, mc_stream_t stream) {
+  if (nframes == 0) return MC_OK;
+  if (!frame_table || !frame_bases || !workspace || !cbytes_out) return MC_EINVAL;
+  if (nframes > 0x7fffffffu || nblocks > 0x7fffffffu || nblocks < nframes || nsegments > 0x7fffffffu ||
+      nsegments < nblocks || nsequences > 0xffffffffu)
+    return MC_EINVAL;
+  if (((uintptr_t)workspace & 7) || ((uintptr_t)frame_table & 7) || ((uintptr_t)cbytes_out & 3) ||
+      ((uintptr_t)frame_bases & 3))
+    return MC_EINVAL;
+  const size_t nstreams = nblocks;  // do-not-split: a stream is a block
+  const z_layout w = z_plan(nstreams, nsegments, nsequences);
+  if (workspace_bytes < w.scratch) return MC_ENOSPC;
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t *ws = static_cast<uint8_t *>(workspace);
+  uint32_t *words = reinterpret_cast<uint32_t *>(ws + w.words);
+  z_args z;
+  enc_args &a = z.e;
+  a.base = (uint64_t)(uintptr_t)src;
+  a.table = static_cast<const mc_blosc_enc_frame *>(frame_table);
+  a.nframes = (uint32_t)nframes, a.nblocks = (uint32_t)nblocks, a.nstreams = (uint32_t)nstreams;
+  a.scratch = ws + w.scratch;
+  a.scratch_bytes = workspace_bytes - w.scratch;
+  a.csize = words, a.out_off = words + nstreams, a.frame_mode = words + 2 * nstreams;
+  a.cbytes_out = cbytes_out;
+  z.bases = frame_bases;
+  z.chunks = reinterpret_cast<mc_zstd_enc_chunk *>(ws + w.chunks);
+  z.zsize = reinterpret_cast<uint32_t *>(ws + w.zsize);
+  z.zerr = reinterpret_cast<int32_t *>(ws + w.zerr);
+  z.nsegs = (uint32_t)nsegments, z.nseqs = nsequences;
+  const unsigned sgrid = (unsigned)((nstreams + MC_BLOCK - 1) / MC_BLOCK);
+  hipLaunchKernelGGL(z_chunks_kernel, dim3(sgrid), dim3(MC_BLOCK), 0, st, z);
+  int rc = mc_last_launch();
+  if (rc != MC_OK) return rc;
+  // parse, code, layout, emit: the `zstd` encoder's own four launches (absolute addresses: no base)
+  rc = mc_zstd_encode_batch(nullptr, z.chunks, nstreams, nsegments, nsequences, ws + w.zws, w.scratch - w.zws, z.zsize,
+                            z.zerr, stream);
+  if (rc != MC_OK) return rc;
+  hipLaunchKernelGGL(z_bridge_kernel, dim3(sgrid), dim3(MC_BLOCK), 0, st, z);
+  rc = mc_last_launch();
   if (rc != MC_OK) return rc;
   hipLaunchKernelGGL(layout_kernel, dim3((unsigned)nframes), dim3(MC_BLOCK), 0, st, a);
   rc = mc_last_launch();

@@ -82,6 +82,7 @@ struct mc_blosc_frame {
 
 #define MC_LZ4_S_RAW 1u    // stored: copy cbytes bytes
 #define MC_LZ4_S_VALID 2u  // cleared when the plan rejected the block
+#define MC_LZ4_S_FORMAT_SHIFT 8u  // above it: the frame's format, where the caller's plan kernel notes it (mc_blosc_z.h)
 
 // One stream, as the plan kernel leaves it for the decode kernel.
 struct mc_lz4_stream {

@@ -237,6 +237,35 @@ MC_DEV int decode_wave(const uint8_t *__restrict__ src, uint32_t n, uint8_t *__r
 }
 
 // the LDS history ring for streams of at most max_stream bytes
+// first error of a frame wins; plain vector atomics / stores
+MC_DEV void record_error(int32_t *err, uint32_t frame, int code, uint32_t stream) {
+  if (atomicCAS(reinterpret_cast<int *>(&err[2 * frame]), 0, code) == 0) err[2 * frame + 1] = (int32_t)stream;
+}
+
+// One stream of a Blosc batch's descriptor list by its wave: a stored stream
+// is a wave-wide copy, another one LZ4 block through decode_wave.  fmt 0:
+// every valid stream; else only the streams whose descriptor carries that
+// format (a launch of mc_blosc_decode_batch_z).  The decode kernel of both
+// Blosc entry points.
+MC_DEV void blosc_lz4_stream(const uint8_t *__restrict__ frames, const mc_lz4_stream *__restrict__ streams,
+                             uint32_t nstreams, uint32_t fmt, uint8_t *ring, uint32_t ring_mask,
+                             int32_t *__restrict__ err) {
+  const uint32_t sidx = blockIdx.x, lane = threadIdx.x;
+  if (sidx >= nstreams) return;
+  const mc_lz4_stream d = streams[sidx];
+  if (!(d.flags & MC_LZ4_S_VALID) || (fmt && (d.flags >> MC_LZ4_S_FORMAT_SHIFT) != fmt)) return;
+  const uint8_t *src = frames + d.src_off;
+  uint8_t *dst = reinterpret_cast<uint8_t *>((uintptr_t)d.dst);
+  const uint32_t n = uni(d.cbytes), usize = uni(d.usize);
+  if (d.flags & MC_LZ4_S_RAW) {  // cbytes == usize (plan)
+    for (uint32_t k = lane; k < usize; k += WAVE) dst[k] = src[k];
+    return;
+  }
+  uint32_t produced;
+  const int e = decode_wave(src, n, dst, usize, ring, ring_mask, lane, &produced);
+  if (e != MC_LZ4_OK && lane == 0) record_error(err, d.frame, e, sidx);
+}
+
 inline uint32_t ring_bytes(size_t max_stream) {
   uint32_t r = 256;
   while (r < max_stream && r < 65536u) r <<= 1;
