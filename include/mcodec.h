@@ -45,6 +45,7 @@
  *   mc_deflate_encode_batch ........ zlib.py / gzip.py encode
  *   mc_zstd_decode_batch ........... zstd.pyx:183-277 decompress
  *   mc_zstd_encode_batch ........... zstd.pyx:96-180 compress
+ *   mc_bz2_decode_batch ............ bz2.py decode
  *   *_batch ........................ no reference counterpart: the Zarr caller loops
  *                                    Codec.encode per chunk; these run B equal-size
  *                                    chunks in one launch (chunk b at base + b*stride).
@@ -846,6 +847,50 @@ int mc_zstd_size_batch(const void *frames, const void *frame_table, size_t nfram
 int mc_zstd_decode_batch(const void *frames, const void *frame_table, size_t nframes,
                          size_t max_capacity, void *workspace, size_t workspace_bytes,
                          uint32_t *produced, int32_t *err, mc_stream_t stream);
+
+/* ---- bz2 decode: bzip2 streams (bz2.py) ----------------------------------- */
+/* Decode a batch of bzip2 streams (one stream each).  The rules and the error
+ * codes are csrc/mc_bz2.h's (libbz2 1.0.8's acceptance; a randomised block and
+ * a further stream are refused with codes of their own).
+ *   frames       device: the frames' bytes, concatenated
+ *   frame_table  device, 8-B aligned: nframes records of 32 bytes, the inflate
+ *                record: u64 src_off, u64 src_len (< 2^30), u64 dst (device
+ *                address of the output), u32 capacity (bytes dst holds, < 2^30;
+ *                dst may be 0 when it is 0), u32 reserved (0)
+ *   max_level    1..9: the highest level digit ("BZh1".."BZh9") of the batch,
+ *                read by the caller from the frames' first four bytes; a frame
+ *                of a higher level is refused (MC_BZ2_E_TABLE)
+ *   multi_min    0, or the block size (in symbols) from which the inverse BWT
+ *                goes multi-start instead of taking the one-lane chase: 0 is
+ *                the measured default (2048); another value is for an A/B run
+ *   workspace    device, 8-B aligned, mc_bz2_workspace(nframes, max_level)
+ *                bytes: the stream records and, per resident wave (at most 768,
+ *                not per frame), 5 bytes x 100000 x max_level
+ *   err          device: 2 * nframes int32, zeroed here; frame i leaves
+ *                err[2i] = 0 or a positive code and err[2i+1] = the blocks
+ *                completed before it
+ * Both calls are a plan launch (one thread per frame: the header and the
+ * level) and a launch of min(nframes, 768) waves that take frames from a
+ * counter and walk a frame's blocks in order: entropy stage, counting sort,
+ * inverse BWT (multi-start over splitters for all but small blocks), RLE1 undo
+ * and CRC (csrc/mc_bz2.hip).  mc_bz2_size_batch compiles the output stores
+ * out: sizes[i] = the bytes frame i decodes to; dst and capacity are not used;
+ * every check of the decode, the CRCs included, is made.  mc_bz2_decode_batch:
+ * produced[i] = the bytes written to dst.  A frame that would produce more
+ * than its capacity is refused and nothing outside [dst, dst + capacity) is
+ * written; nothing outside a frame is read.
+ * Return a launch status; the records are valid once the stream has run.
+ * Present from this release on; mc_abi_version() is unchanged, callers find
+ * the three by symbol. */
+size_t mc_bz2_workspace(size_t nframes, unsigned max_level);
+int mc_bz2_size_batch(const void *frames, const void *frame_table, size_t nframes,
+                      unsigned max_level, unsigned multi_min, void *workspace,
+                      size_t workspace_bytes, uint32_t *sizes, int32_t *err,
+                      mc_stream_t stream);
+int mc_bz2_decode_batch(const void *frames, const void *frame_table, size_t nframes,
+                        unsigned max_level, unsigned multi_min, void *workspace,
+                        size_t workspace_bytes, uint32_t *produced, int32_t *err,
+                        mc_stream_t stream);
 
 /* ---- zlib / gzip encode: DEFLATE with dynamic Huffman codes per 64 KiB ---- */
 /* Encode a batch of chunks as zlib (RFC 1950) or gzip (RFC 1952) frames.  The

@@ -65,6 +65,7 @@ from . import gzip  # noqa: E402,F401  (gzip frames, decode; gzip.register() reg
 from . import deflate  # noqa: E402,F401  (zlib / gzip frames, encode; deflate.register() registers both directions)
 from . import zstd  # noqa: E402,F401  (Zstandard frames, decode; zstd.register() registers it)
 from . import zstd_enc  # noqa: E402,F401  (Zstandard frames, encode; zstd_enc.register() registers both directions)
+from . import bz2  # noqa: E402,F401  (bzip2 streams, decode; bz2.register() registers it)
 from . import chunks  # noqa: E402,F401  (Zarr-style batched / host-streamed chunk pipelines)
 from . import graphs  # noqa: E402,F401  (HIP-graph captured chunk pipelines)
 
@@ -96,6 +97,7 @@ __all__ = [
     "zlib",
     "zstd",
     "zstd_enc",
+    "bz2",
     "codec_registry",
     "get_codec",
     "register_codec",

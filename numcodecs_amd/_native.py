@@ -203,6 +203,9 @@ _SIGNATURES = {
     "mc_blosc_encode_batch_z": [_c_vp, _c_vp, _c_vp, _c_size, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp],
     "mc_zstd_encode_workspace": [_c_size, _c_size, _c_size],
     "mc_zstd_encode_batch": [_c_vp, _c_vp, _c_size, _c_size, _c_size, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
+    "mc_bz2_workspace": [_c_size, ctypes.c_uint],
+    "mc_bz2_size_batch": [_c_vp, _c_vp, _c_size, ctypes.c_uint, ctypes.c_uint, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
+    "mc_bz2_decode_batch": [_c_vp, _c_vp, _c_size, ctypes.c_uint, ctypes.c_uint, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
 }
 _RESTYPES = {
     "mc_host_device_pointer": ctypes.c_void_p,
@@ -225,6 +228,7 @@ _RESTYPES = {
     "mc_deflate_encode_workspace": ctypes.c_size_t,
     "mc_zstd_workspace": ctypes.c_size_t,
     "mc_zstd_encode_workspace": ctypes.c_size_t,
+    "mc_bz2_workspace": ctypes.c_size_t,
     "mc_blosc_decode_batch_z_workspace": ctypes.c_size_t,
     "mc_blosc_encode_batch_z_workspace": ctypes.c_size_t,
 }
