@@ -46,6 +46,7 @@
  *   mc_zstd_decode_batch ........... zstd.pyx:183-277 decompress
  *   mc_zstd_encode_batch ........... zstd.pyx:96-180 compress
  *   mc_bz2_decode_batch ............ bz2.py decode
+ *   mc_bz2_encode_batch ............ bz2.py encode
  *   *_batch ........................ no reference counterpart: the Zarr caller loops
  *                                    Codec.encode per chunk; these run B equal-size
  *                                    chunks in one launch (chunk b at base + b*stride).
@@ -890,6 +891,49 @@ int mc_bz2_size_batch(const void *frames, const void *frame_table, size_t nframe
 int mc_bz2_decode_batch(const void *frames, const void *frame_table, size_t nframes,
                         unsigned max_level, unsigned multi_min, void *workspace,
                         size_t workspace_bytes, uint32_t *produced, int32_t *err,
+                        mc_stream_t stream);
+
+/* ---- bz2 encode: bzip2 streams, one sorted block per segment (bz2.py) ------ */
+/* Encode a batch of chunks as bzip2 streams at one level.  The format -- a
+ * chunk cut into input segments of 80000 * level - 16 bytes, one block each,
+ * blocks joined at bit granularity -- the bound and the scalar encoder the
+ * kernels reproduce byte for byte are csrc/mc_bz2_enc.h's.  Five launches for
+ * the whole batch (csrc/mc_bz2_enc.hip): prepare (a wave per block: CRC, RLE1,
+ * in-use map), sort (a workgroup per block, at most 256 resident, blocks taken
+ * from a counter: the forward BWT by prefix doubling), code (a wave per block:
+ * MTF, zero runs, the Huffman tables, both exact costs and the choice), layout
+ * (a workgroup per chunk: bit offsets, the frame's size against its slot, the
+ * frame cleared, stream header, CRC chain, trailer) and emit (a wave per
+ * block: the bits).
+ *   chunk_table  device, 8-B aligned: nchunks records of 32 bytes, one per
+ *                chunk with nbytes > 0, in block order: u64 src (device
+ *                address), u64 dst (device address of the output slot), u32
+ *                nbytes (1 ... 2^30 - 1), u32 dst_cap (the slot's bytes;
+ *                mc_bz2_encode_bound(nbytes, level) always suffice), u32
+ *                block_base (index of the chunk's first block in the batch),
+ *                u32 reserved
+ *   nblocks      the batch's blocks: the sum of ceil(nbytes / (80000 * level - 16))
+ *   max_chunk    the largest nbytes of the batch (it sizes the per-block arrays)
+ *   workspace    device, 8-B aligned, mc_bz2_encode_workspace(nchunks, nblocks,
+ *                max_chunk, level) bytes: per block about 4 bytes a symbol, and
+ *                per resident sort workgroup (min(nblocks, 256), not per block)
+ *                16 bytes a symbol; a block holds at most 5/4 of min(max_chunk,
+ *                80000 * level - 16) symbols
+ *   cbytes_out   device: nchunks u32: the frame's size, 0 when it was refused
+ *   err          device: 2 * nchunks int32, zeroed here; chunk i leaves
+ *                err[2i] = 0 or a code of csrc/mc_bz2_enc.h (1: the frame does
+ *                not fit dst_cap, err[2i+1] = its size, nothing written; 2: the
+ *                record is out of range)
+ * The aligned dwords of memory that hold a frame's first and last bytes are
+ * updated with atomic ORs; their bytes outside the frame keep their values.
+ * Returns a launch status; the records are valid once the stream has run.
+ * Present from this release on; mc_abi_version() is unchanged, callers find
+ * the three by symbol. */
+size_t mc_bz2_encode_bound(size_t nbytes, unsigned level);
+size_t mc_bz2_encode_workspace(size_t nchunks, size_t nblocks, size_t max_chunk, unsigned level);
+int mc_bz2_encode_batch(const void *chunk_table, size_t nchunks, size_t nblocks,
+                        size_t max_chunk, unsigned level, void *workspace,
+                        size_t workspace_bytes, uint32_t *cbytes_out, int32_t *err,
                         mc_stream_t stream);
 
 /* ---- zlib / gzip encode: DEFLATE with dynamic Huffman codes per 64 KiB ---- */

@@ -206,6 +206,9 @@ _SIGNATURES = {
     "mc_bz2_workspace": [_c_size, ctypes.c_uint],
     "mc_bz2_size_batch": [_c_vp, _c_vp, _c_size, ctypes.c_uint, ctypes.c_uint, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
     "mc_bz2_decode_batch": [_c_vp, _c_vp, _c_size, ctypes.c_uint, ctypes.c_uint, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
+    "mc_bz2_encode_bound": [_c_size, ctypes.c_uint],
+    "mc_bz2_encode_workspace": [_c_size, _c_size, _c_size, ctypes.c_uint],
+    "mc_bz2_encode_batch": [_c_vp, _c_size, _c_size, _c_size, ctypes.c_uint, _c_vp, _c_size, _c_vp, _c_vp, _c_vp],
 }
 _RESTYPES = {
     "mc_host_device_pointer": ctypes.c_void_p,
@@ -229,6 +232,8 @@ _RESTYPES = {
     "mc_zstd_workspace": ctypes.c_size_t,
     "mc_zstd_encode_workspace": ctypes.c_size_t,
     "mc_bz2_workspace": ctypes.c_size_t,
+    "mc_bz2_encode_bound": ctypes.c_size_t,
+    "mc_bz2_encode_workspace": ctypes.c_size_t,
     "mc_blosc_decode_batch_z_workspace": ctypes.c_size_t,
     "mc_blosc_encode_batch_z_workspace": ctypes.c_size_t,
 }
